@@ -34,7 +34,12 @@ s16 tracks, 64/N tracks on each device, int32 partials -> one exchange
 torch.distributed reduce_scatter_tensor over RCCL under torchrun) ->
 saturate on the device that owns each block of mixes.
 
-Also reported (one JSON line on rank 0):
+A plain run sets up, warms up, times --steps steps, writes its outputs when
+--dump-outputs is given and prints one JSON line (rank 0) with the headline
+figure and the roofline of the timed steps themselves.  cpu_baseline,
+parity_check and box are measured only with --full.
+
+Reported:
   roofline     — algorithmic bytes per launch (inputs read once + output
                  written once) / average kernel duration from HIP events on
                  the stream the kernel runs on, vs the 8 TB/s HBM peak;
@@ -42,7 +47,7 @@ Also reported (one JSON line on rank 0):
                  profiles/*traffic*.json taken on the same kernel sources
                  (sha256 of KERNEL_SOURCES; an earlier rocprofv3 pass, the
                  file named in traffic_source), else null.
-  cpu_baseline — the library's own host CPU backend (n_devices = 0,
+  cpu_baseline — (--full) the library's own host CPU backend (n_devices = 0,
                  xm-audio-utils_amd/src/cpu: the same C API call, bit-identical
                  results) on a bounded sample of the same workload, in a child
                  process on this process's allotted host cores
@@ -50,8 +55,13 @@ Also reported (one JSON line on rank 0):
                  The reference has no code, so this C path is
                  the "reference CPU path" of BASELINE.json:5; oracle/ stays
                  the checker.
-  parity_check — after the timed loop every shard's first and last mix are
-                 bit-compared with the oracle (true = all equal).
+  parity_check — (--full) after the timed loop every shard's first and last
+                 mix are bit-compared with the oracle (true = all equal).
+
+--dump-outputs DIR writes what the last timed step left in the output buffers
+as float32 DIR/<name>.npy (dump_outputs below): whole mixes and one window of
+every mix, a fixed seeded choice, under 64 MB in all.  The inputs are the
+same from run to run, so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -117,12 +127,21 @@ def parse(argv=None):
     ap.add_argument("--cpu-mixes", type=int, default=48, help="mixes in the CPU-baseline sample")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="target wall time of the CPU-baseline sample")
     ap.add_argument("--cpu-only", action="store_true", help=argparse.SUPPRESS)   # the baseline's child process
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, bit-compare with the oracle and name the box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write a fixed sample of the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--fill", choices=["synth", "zero", "tiny"], default="synth",
                     help="dev only: input data (synth = the bench's synthetic PCM)")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-timing parity check")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the post-timing parity check")
     ap.add_argument("--check", action="store_true", help=argparse.SUPPRESS)   # the default now
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # the plain run: the headline figure only
+        args.no_cpu = args.no_check = True
+    return args
 
 
 def plan(args, world: int, visible: int):
@@ -320,6 +339,34 @@ def parity_check(x, y, idx, ramps):
     return bool(np.array_equal(got.view(np.uint32), ref.view(np.uint32)))
 
 
+DUMP_BUDGET = 60 * 1000 * 1000   # bytes of float32 over all shards (< 64 MB with the .npy headers)
+DUMP_WINDOW = 8192               # most frames of every mix in <name>_windows
+
+
+def dump_outputs(args, y, name, shards=1):
+    """--dump-outputs: a fixed sample of one shard's output buffer y [mixes,
+    frames, channels], as the caller's buffer holds it after the last timed
+    step, converted to float32 (exact for s16).  <name>_mixes.npy: whole mixes
+    (the first, the last and a seeded choice between); <name>_windows.npy:
+    up to DUMP_WINDOW frames of every mix from a seeded start frame (at most
+    half of the shard's budget).  The choice depends on the seed and the shape
+    only."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    B, F, C = y.shape
+    budget = DUMP_BUDGET // (4 * shards)           # float32 values of this shard
+    rng = np.random.default_rng(SEED)
+    W = max(1, min(F, DUMP_WINDOW, budget // (2 * B * C)))
+    k = int(max(1, min(B, (budget - B * W * C) // (F * C))))
+    idx = [0, B - 1][:min(k, B)]
+    idx = sorted(idx + [int(b) for b in rng.permutation(B) if b not in (0, B - 1)][:k - len(idx)])
+    starts = torch.as_tensor(rng.integers(0, F - W + 1, size=B), device=y.device)
+    whole = y[torch.as_tensor(idx, device=y.device)].float().cpu().numpy()
+    rows = torch.arange(B, device=y.device)[:, None]
+    win = y[rows, starts[:, None] + torch.arange(W, device=y.device)[None, :]].float().cpu().numpy()
+    np.save(os.path.join(args.dump_outputs, f"{name}_mixes.npy"), whole)
+    np.save(os.path.join(args.dump_outputs, f"{name}_windows.npy"), win)
+
+
 def headline_line(args, *, n_gpus, shards, B, ntr, N, F, value, ms_per_step, kern_ms, launches, ok, parallelism,
                   ramps, mode):
     in_samples = B * ntr * N * 2
@@ -437,6 +484,8 @@ def run_headline_ranked(args):
     if not args.no_check:   # every rank: its first and last mix vs the oracle
         ok = parity_check(x, y, sorted({0, B - 1}), ramps)
         ok = xd.min_over_ranks(rk, ok, device=cdev)
+    if args.dump_outputs:
+        dump_outputs(args, y, f"rank{rank}" if world > 1 else "out", world)
 
     if rank == 0:
         value = world * B * ntr * N * 2 / (elapsed / args.steps) / 1e6
@@ -493,6 +542,9 @@ def run_headline_local(args, devs):
     ok = None
     if not args.no_check:
         ok = all(parity_check(x, y, sorted({0, B - 1}), ramps) for x, y in zip(xs, ys))
+    if args.dump_outputs:
+        for d, y in enumerate(ys):
+            dump_outputs(args, y, f"shard{d}" if n > 1 else "out", n)
     value = n * B * ntr * N * 2 / (elapsed / args.steps) / 1e6
     par = (f"dp{n} (independent mixes, no collective), one process, in-library multi-device handle over "
            f"devices {devs}")
@@ -581,6 +633,9 @@ def run_c5_local(args, devs):
                 g = d * nb + b   # global mix: its tracks are block b of every shard
                 xm_ = np.concatenate([xs[q][g].cpu().numpy() for q in range(n)])
                 ok &= c5_check(xm_, ys[d][b].cpu().numpy(), ramps)
+    if args.dump_outputs:
+        for d, y in enumerate(ys):
+            dump_outputs(args, y, f"shard{d}" if n > 1 else "out", n)
     distinct = len(set(devs)) == n
     par = (f"{n} shards, tracks of every mix split over devices {devs}; exchange: "
            + ("in-library RCCL ncclReduceScatter(int32) over xGMI, in chunks overlapped with the partials"
@@ -644,6 +699,8 @@ def run_c5_ranked(args):
                     mine = [t.cpu().numpy() for t in bufs]
             ok &= c5_check(np.concatenate(mine), y[b].cpu().numpy(), ramps)
         ok = xd.min_over_ranks(rk, ok, device="cuda")
+    if args.dump_outputs:
+        dump_outputs(args, y, f"rank{rk.rank}" if rk.world > 1 else "out", rk.world)
     if rk.rank == 0:
         par = (f"{rk.world} ranks, one process per GPU; exchange: torch.distributed reduce_scatter_tensor (RCCL), "
                "asynchronous, in chunks overlapped with the partials")
@@ -687,7 +744,8 @@ def main(argv=None):
     if args.cpu_only:
         run_cpu_only(args)
         return
-    box_ids()   # before any device work
+    if args.full:
+        box_ids()   # before any device work
     world = int(os.environ.get("WORLD_SIZE", "1"))
     mode, devs = plan(args, world, torch.cuda.device_count())
     if args.config == "c5":

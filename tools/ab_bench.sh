@@ -4,7 +4,7 @@
 # N rounds, each run under its own limit.   tools/ab_bench.sh [rounds] [bench args]
 set -o pipefail
 N=${1:-3}; shift
-ARGS=${@:---steps 20 --warmup 5 --no-cpu}
+ARGS=${@:---steps 20 --warmup 5 --full --no-cpu}
 mkdir -p gpurun_out/ab
 LA=xm-audio-utils_amd/lib/libxm_audio.so
 LB=xm-audio-utils_amd/lib_ab/libxm_audio.so

@@ -18,4 +18,4 @@ envs() {   # spec -> env words
 for rnd in 1 2; do
   for sp in "${specs[@]}"; do run "${sp%%:*}" "" $(envs "$sp") || exit 1; done
 done
-for sp in "${specs[@]}"; do run "${sp%%:*}_chk" --check $(envs "$sp") || exit 1; done
+for sp in "${specs[@]}"; do run "${sp%%:*}_chk" "--full --check" $(envs "$sp") || exit 1; done

@@ -9,7 +9,7 @@ R=$1; shift
 LIBS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 [ "$1" = "--" ] && shift
-ARGS=${@:---steps 20 --warmup 5 --no-cpu}
+ARGS=${@:---steps 20 --warmup 5 --full --no-cpu}
 mkdir -p gpurun_out/ab
 for i in $(seq 1 $R); do
   for l in "${LIBS[@]}"; do

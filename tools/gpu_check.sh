@@ -14,7 +14,7 @@ done
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-DRIVER="--gpus 1 --steps 20 --warmup 5"          # the driver's bench command line
+DRIVER="--gpus 1 --steps 20 --warmup 5 --full"   # the bench line with its CPU baseline and parity check
 PMCB="--steps 3 --warmup 1 --no-cpu --no-check"
 step() {   # step <name> <seconds> <cmd...>
   local name=$1 secs=$2; shift 2

@@ -28,15 +28,15 @@ if [ $TESTS = 1 ]; then
   step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ $BENCH = 1 ]; then
-  step bench 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 5
-  step bench_dev00 400 python3 -u bench.py --devices 0,0 --steps 10 --warmup 3 --no-cpu
+  step bench 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --full
+  step bench_dev00 400 python3 -u bench.py --devices 0,0 --steps 10 --warmup 3 --full --no-cpu
   echo "== bench --gpus 2 on a 1-GPU box (must fail loudly)"
   if timeout -k 10 120 python3 bench.py --gpus 2 --steps 1 --warmup 0 --no-cpu > $OUT/bench_gpus2.log 2>&1; then
     echo "== bench --gpus 2 did NOT fail"; exit 1
   fi
   tail -n 2 $OUT/bench_gpus2.log
-  step bench_c5 400 python3 -u bench.py --config c5 --steps 5 --warmup 2
-  step bench_c5_dev8 400 python3 -u bench.py --config c5 --devices 0,0,0,0,0,0,0,0 --steps 5 --warmup 2 --no-cpu
+  step bench_c5 400 python3 -u bench.py --config c5 --steps 5 --warmup 2 --full
+  step bench_c5_dev8 400 python3 -u bench.py --config c5 --devices 0,0,0,0,0,0,0,0 --steps 5 --warmup 2 --full --no-cpu
 fi
 if [ -n "$CFGS" ]; then
   step configs 900 python3 -u tools/bench_configs.py $CFGS

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 timeout -k 10 300 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -k "$K" > $OUT/pytest.log 2>&1
 rc=$?; tail -n 3 $OUT/pytest.log; [ $rc -ne 0 ] && exit $rc
 for i in 1 2 3; do
-  timeout -k 10 200 python3 -u bench.py --steps 20 --warmup 5 --no-cpu > $OUT/bench$i.log 2>&1 || { tail -5 $OUT/bench$i.log; exit 1; }
+  timeout -k 10 200 python3 -u bench.py --steps 20 --warmup 5 --full --no-cpu > $OUT/bench$i.log 2>&1 || { tail -5 $OUT/bench$i.log; exit 1; }
   grep '^{' $OUT/bench$i.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench', d['ms_per_step'], d['roofline']['frac'], d['parity_check'])"
 done
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU -d $OUT/pmc_sq -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-check > $OUT/pmc_sq.log 2>&1 || { tail -5 $OUT/pmc_sq.log; exit 1; }

@@ -91,7 +91,7 @@ def trace_bench(src, dst):
     timed = durs[-line["steps"]:]
     avg_ms = sum(timed) / len(timed) / 1e6
     alg = line["roofline"]["alg_bytes_per_launch"]
-    rec = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5",
+    rec = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full",
            "bench_line": line,
            "rocprof_timed_launches": len(timed),
            "rocprof_avg_launch_ms": avg_ms,
