@@ -1,5 +1,5 @@
 /*
- * xm_effects.h — biquad / FIR effects chain over batches of clips (C ABI).
+ * xm_effects.h — biquad / FIR / comb effects chain over batches of clips (C ABI).
  *
  * BUILD-OWNED ABI (reference has no headers: /root/reference/README.md:1;
  * prefix xm_effects_* from BASELINE.json:5, signatures from SURVEY.md §8(b)).
@@ -12,7 +12,20 @@
  *  FIR of K taps, causal, output length = input length:
  *      acc=+0; for t=0..K-1: acc = acc + x[n-K+1+t]*h[K-1-t]   (x<0 := 0)
  *  (scipy upfirdn(h, x)[:N], _upfirdn.py:107)
- *  Effects run in insertion order; consecutive biquads form one cascade.
+ *  comb (delay line: echo, feedback comb, Schroeder all-pass) of D frames,
+ *  coefficients (b0, bd, ad), per clip on the interleaved sample stream of
+ *  frames*C samples with lag Ds = D*C, so channels never mix:
+ *      y[i] = b0*x[i] + ( bd*x[i-Ds] - ad*y[i-Ds] )
+ *      p = b0*x[i];  q = bd*x[i-Ds];  r = ad*y[i-Ds];  t = q - r;  y[i] = p + t
+ *  every operation fp32, round-to-nearest-even, separately rounded (no
+ *  contraction), denormals preserved; x[i] = y[i] = +0 for i < 0 (when
+ *  streaming: the carried history).  The operations are carried out as written
+ *  also where an operand is the zero padding: the sign of a zero result is
+ *  part of the contract.
+ *  (scipy lfilter(b, a, x) in float32 with b = [b0, 0, ..., bd] and
+ *  a = [1, 0, ..., ad], both of length D+1)
+ *  Effects run in insertion order; consecutive biquads form one cascade; a
+ *  comb is a stage of its own and never merges with its neighbours.
  */
 #ifndef XM_EFFECTS_H
 #define XM_EFFECTS_H
@@ -78,9 +91,27 @@ XM_API int xm_effects_add_eq_band(XmEffects *e, int band, double f0_hz, double g
 /* FIR with K taps (1 <= K <= 4096), copied. */
 XM_API int xm_effects_add_fir(XmEffects *e, const float *h, int K);
 
+/* Comb stage y[n] = b0*x[n] + (bd*x[n-D] - ad*y[n-D]) per channel (the
+ * arithmetic above), 1 <= delay_frames <= XM_MAX_DELAY, finite coefficients
+ * (XM_EINVAL otherwise; XM_ENOMEM beyond 128 effects).  Stability (|ad| < 1)
+ * is not checked: the contract covers the arithmetic only. */
+#define XM_MAX_DELAY (1 << 20)
+XM_API int xm_effects_add_comb(XmEffects *e, int64_t delay_frames, float b0, float bd, float ad);
+
+/* Echo y[n] = x[n] + wet*x[n-D] + feedback*y[n-D]: add_comb(D, 1, (float)wet,
+ * -(float)feedback) with D = llrint(delay_ms * rate / 1000.0) in fp64, ties
+ * to even; XM_EINVAL if D is outside [1, XM_MAX_DELAY]. */
+XM_API int xm_effects_add_echo(XmEffects *e, double delay_ms, double feedback, double wet);
+
+/* Schroeder all-pass y[n] = -g*x[n] + x[n-D] + g*y[n-D]: add_comb(D,
+ * -(float)g, 1, -(float)g), D as for add_echo. */
+XM_API int xm_effects_add_allpass(XmEffects *e, double delay_ms, double g);
+
 /* Number of effects and the coefficients of biquad i (for inspection). */
 XM_API int xm_effects_count(const XmEffects *e);
 XM_API int xm_effects_get_biquad(const XmEffects *e, int index, float sos[6]);
+/* Delay and coef = {b0, bd, ad} of comb i; XM_EINVAL when effect i is not a comb. */
+XM_API int xm_effects_get_comb(const XmEffects *e, int index, int64_t *delay_frames, float coef[3]);
 
 /* Install a caller-owned hipStream_t (NULL: the chain's own stream, which is
  * created blocking: ordered after the legacy default stream's work, as a
@@ -96,9 +127,10 @@ XM_API int xm_effects_process_batch(XmEffects *e, const float *const *in, float 
  * n_clips streams at zero state for the chain as it is now; every
  * xm_effects_process_stream() call filters the next `frames` frames of each
  * stream (in[i] / out[i] as process_batch, in == out allowed), carrying on
- * the device the biquad state (z0, z1 per section and channel) and the last
- * K-1 input frames of every FIR stage.  Any split of a signal into blocks
- * (ragged, 1-frame or empty blocks) gives, bit for bit, the output of one
+ * the device the biquad state (z0, z1 per section and channel), the last
+ * K-1 input frames of every FIR stage and the last D input and D output
+ * frames of every comb stage.  Any split of a signal into blocks (ragged,
+ * 1-frame or empty blocks, longer or shorter than D) gives, bit for bit, the output of one
  * process_batch() over the whole signal.  Adding an effect ends the streams:
  * process_stream then fails with XM_EINVAL until the next reset, as it does
  * for an n_clips other than the reset's. */

@@ -24,6 +24,8 @@ planar  48k -> 44.1k fp32, planar tracks and mixes (fused kernel, PL)
 conv    48k -> 44.1k, s16 tracks into the fp32 mix (fused kernel, IO 1)
 stream  the headline pushed in 8 blocks through stream_push (fused bulk straight from the block + generic heads)
 oconv   the headline with XM_MIXER_OUT_CONVERT: s16 output (fused kernel epilogue)
+comb    comb stage alone, D = 11025 frames (250 ms echo), 1024 stereo 10 s fp32 clips in place (k_comb_wide)
+comb1   the same with D = 1 (k_comb_narrow); both report vs_copy against a torch device copy of the same bytes
 Unit: input samples (frames x channels x tracks) per second; roofline
 fraction = algorithmic bytes (inputs once + output once) / kernel time / 8 TB/s.
 Inputs are synthetic PCM generated in HBM (xm_synth_pcm), outside the timing.
@@ -355,6 +357,46 @@ def bq(a):
                          "achieved_GBps": round(alg / (k * 1e-3) / 1e9, 1),
                          "frac": round(alg / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "parity_check": ok}
+    print(json.dumps(line), flush=True)
+
+
+def comb(a): _comb(a, "comb", 11025)   # 250 ms echo: the wide-lag kernel (k_comb_wide)
+def comb1(a): _comb(a, "comb1", 1)     # 1-frame lag: the narrow-lag kernel (k_comb_narrow)
+
+
+def _comb(a, name, D):
+    """Comb stage alone: echo coefficients over 1024 stereo 10 s clips @ 44.1
+    kHz, device memory, in place; vs_copy = its time over a torch
+    device-to-device copy of the same bytes, timed the same way."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from comb_ref import comb_f32
+    B, N = a.clips_fx, 441000
+    coef = (1.0, 0.5, -0.45)
+    e = xm.Effects(44100, 2, mem="device")
+    e.add_comb(D, *coef)
+    x = torch.empty((B, N, 2), dtype=torch.float32, device="cuda")
+    s = torch.cuda.current_stream()
+    xm.synth(x.data_ptr(), "f32", SEED, 0, B, 2, N, 0, s.cuda_stream)
+    x0 = x[ends(B)].clone()
+    e.set_stream(s.cuda_stream)
+    ptrs = [x[b].data_ptr() for b in range(B)]
+    # one checked pass, then timed passes (in place: each pass filters the previous output)
+    e.process_ptrs(ptrs, ptrs, N)
+    torch.cuda.synchronize()
+    ok = parity(a, lambda: all(beq(x[b].cpu().numpy(), comb_f32(x0[i].cpu().numpy(), D, *coef))
+                               for i, b in enumerate(ends(B))))
+    xm.synth(x.data_ptr(), "f32", SEED, 0, B, 2, N, 0, s.cuda_stream)   # timed passes start from bounded input again
+    w, k = timed(lambda: e.process_ptrs(ptrs, ptrs, N), a.steps, a.warmup, s)
+    y = torch.empty_like(x)
+    _, kc = timed(lambda: y.copy_(x), a.steps, a.warmup, s)
+    alg = 2 * B * N * 2 * 4
+    line = {"config": name, "delay_frames": D,
+            "workload": f"comb D={D} (echo), {B} stereo 10 s fp32 clips @ 44.1 kHz, in place",
+            "value": round(B * N * 2 / (w * 1e-3) / 1e6, 1), "unit": "Msamples/s", "ms_per_step": round(w, 4),
+            "kernel_ms": round(k, 4), "copy_ms": round(kc, 4), "vs_copy": round(k / kc, 3),
+            "roofline": {"bound": "hbm", "alg_bytes": alg, "achieved_GBps": round(alg / (k * 1e-3) / 1e9, 1),
+                         "frac": round(alg / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+            "parity": ok, "parity_check": ok}
     print(json.dumps(line), flush=True)
 
 

@@ -894,6 +894,235 @@ __global__ __launch_bounds__(256) void k_fir_hist(XmhFxJob j)
     }
 }
 
+// ---- comb (delay line: echo, feedback comb, all-pass; include/xm_effects.h) ---
+// y[i] = b0*x[i] + (bd*x[i-Ds] - ad*y[i-Ds]) on a clip's interleaved samples,
+// Ds = D * channels.  Position p of [0, Ds) is a chain over the blocks
+// b = 0, 1, ...: sample b*Ds + p depends only on sample (b-1)*Ds + p of x and
+// of y.  So a clip has Ds independent chains, the opposite of the biquad, and
+// the stage is copy-shaped: every byte read once and written once, five
+// separately rounded VALU ops per sample.  The chain's owner keeps its
+// previous x and y in registers; after its last block they are the newest
+// sample of the chain, which is exactly the entry of the streaming history
+// (the last Ds samples of history ++ block) at slot (p - n) mod Ds, n the
+// block's samples.  That holds for n < Ds too (a chain without a sample
+// hands its old history on), so streaming costs no extra pass, and in == out
+// is safe by construction: only its owner touches a sample, and reads it
+// before writing it.
+XM_DEV float comb_step(float x, float &px, float &py, float b0, float bd, float ad)
+{
+    const float p = b0 * x, q = bd * px, r = ad * py;
+    const float t = q - r;
+    const float y = p + t;
+    px = x;
+    py = y;
+    return y;
+}
+
+// Wide lag (Ds >= XMG_COMB_WIDE_MIN): a lane owns V consecutive positions and
+// walks the blocks; a wave's accesses are contiguous.  The x loads do not
+// depend on the recurrence: U blocks are in flight per lane (V*U dwords: at
+// 2048 lanes per CU 64 KiB for V = 1, U = 8 and 128 KiB for V = 4, U = 4,
+// against the ~72 KiB that hide an HBM miss).  Block starts are b*Ds samples
+// in and clip bases are float-aligned, so the 16-B accesses of V = 4 are
+// declared 4-B aligned.  A lane with fewer than V positions (the end of the
+// Ds range) or a block with fewer than V samples left (the ragged last
+// block) goes element by element, with bounds.  Grid: (slice of positions,
+// clip), clips beyond the grid's y range by stride.
+template <int V, int U, bool ST>
+__global__ __launch_bounds__(256) void k_comb_wide(XmhFxJob j)
+{
+    const int64_t Ds = j.comb_delay * j.channels, n = j.frames * j.channels;
+    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (p0 >= Ds) return;
+    const int nv = Ds - p0 < V ? (int)(Ds - p0) : V;   // positions this lane owns
+    const float b0 = j.comb_coef[0], bd = j.comb_coef[1], ad = j.comb_coef[2];
+    // global address space: flat accesses would make every wait a full drain
+    // (vmcnt(0) lgkmcnt(0)) and undo the loads issued ahead
+    typedef const __attribute__((address_space(1))) float gcf;
+    typedef __attribute__((address_space(1))) float gf;
+    typedef const __attribute__((address_space(1))) bq_f4u gcf4u;
+    typedef __attribute__((address_space(1))) bq_f4u gf4u;
+    for (int clip = blockIdx.y; clip < j.n_clips; clip += gridDim.y) {
+        gcf *x = (gcf *)j.in_ptrs[clip];
+        gf *y = (gf *)j.out_ptrs[clip];
+        float px[V], py[V], xr[U][V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            px[e] = py[e] = 0.0f;
+            if (ST && e < nv) {
+                px[e] = j.comb_hist_in[(int64_t)clip * 2 * Ds + p0 + e];
+                py[e] = j.comb_hist_in[(int64_t)clip * 2 * Ds + Ds + p0 + e];
+            }
+        }
+        // running pointers: xl / left_l the next block to load and the samples
+        // from it to the clip's end, ys / left_s the same for the next store;
+        // of a block this lane owns [ptr, ptr + m)
+        gcf *xl = x + p0;
+        gf *ys = y + p0;
+        int64_t left_l = n - p0, left_s = n - p0;
+        auto load = [&](float (&v)[V]) {
+            const int m = left_l < nv ? (int)left_l : nv;
+            if (V == 4 && m == 4) {
+                const bq_f4u t = *(gcf4u *)xl;
+#pragma unroll
+                for (int e = 0; e < V; ++e) v[e] = t[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < V; ++e) v[e] = e < m ? xl[e] : 0.0f;
+            }
+            xl += Ds;
+            left_l -= Ds;
+        };
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (left_l > 0) load(xr[u]);
+        // whole rounds: U more whole blocks to load, so U whole blocks to
+        // store; straight-line code, so the waits for the ring are counted
+        // (vmcnt(N)) instead of drains
+        if (nv == V) {
+            while (left_l - (U - 1) * Ds >= V) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    float xv[V];
+#pragma unroll
+                    for (int e = 0; e < V; ++e) xv[e] = xr[u][e];
+                    if (V == 4) {
+                        const bq_f4u t = *(gcf4u *)xl;
+                        bq_f4u o;
+#pragma unroll
+                        for (int e = 0; e < V; ++e) {
+                            xr[u][e] = t[e];
+                            o[e] = comb_step(xv[e], px[e], py[e], b0, bd, ad);
+                        }
+                        *(gf4u *)ys = o;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) {
+                            xr[u][e] = xl[e];
+                            ys[e] = comb_step(xv[e], px[e], py[e], b0, bd, ad);
+                        }
+                    }
+                    xl += Ds;
+                    ys += Ds;
+                }
+                left_l -= U * Ds;
+                left_s -= U * Ds;
+            }
+        }
+        // the rest (and lanes with fewer than V positions), block by block with bounds
+        while (left_s > 0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (left_s > 0) {
+                    float xv[V];
+#pragma unroll
+                    for (int e = 0; e < V; ++e) xv[e] = xr[u][e];
+                    if (left_l > 0) load(xr[u]);   // U blocks ahead, before this block's store in program order
+                    const int m = left_s < nv ? (int)left_s : nv;
+                    if (V == 4 && m == 4) {
+                        bq_f4u o;
+#pragma unroll
+                        for (int e = 0; e < V; ++e) o[e] = comb_step(xv[e], px[e], py[e], b0, bd, ad);
+                        *(gf4u *)ys = o;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < V; ++e)
+                            if (e < m) ys[e] = comb_step(xv[e], px[e], py[e], b0, bd, ad);
+                    }
+                    ys += Ds;
+                    left_s -= Ds;
+                }
+            }
+        }
+        if (ST) {
+            const int64_t sh = n % Ds;
+#pragma unroll
+            for (int e = 0; e < V; ++e)
+                if (e < nv) {
+                    int64_t q = p0 + e - sh;
+                    if (q < 0) q += Ds;
+                    j.comb_hist_out[(int64_t)clip * 2 * Ds + q] = px[e];
+                    j.comb_hist_out[(int64_t)clip * 2 * Ds + Ds + q] = py[e];
+                }
+        }
+    }
+}
+
+// Narrow lag (Ds < XMG_COMB_WIDE_MIN, down to 1): a clip has few chains, so
+// the parallelism comes from clips.  A workgroup takes G clips (G * Ds <= 256
+// chains, one per lane) and walks time in tiles of T = S * Ds samples per
+// clip (G * T <= CN_TILE): all 256 lanes load the tile's G rows into LDS with
+// coalesced loads, the chain lanes walk their S steps inside the tile in
+// place (8 steps' x read ahead of the dependent chain), all lanes store the
+// rows.  The carry between tiles is the chain's registers.  Row pitch
+// TP = T + pad with TP % 32 == Ds % 32: chain lane (g, p) reads
+// g*TP + p + k*Ds, bank (lane + k*Ds) % 32, conflict-free.  Several
+// workgroups per CU overlap one's chain phase with another's loads and stores.
+constexpr int CN_TILE = 4096;
+constexpr int CN_MAXG = 64;
+
+template <bool ST>
+__global__ __launch_bounds__(256) void k_comb_narrow(XmhFxJob j, int G, int S)
+{
+    extern __shared__ float cn_lds[];
+    typedef const __attribute__((address_space(1))) float gcf;
+    typedef __attribute__((address_space(1))) float gf;
+    const int Ds = (int)(j.comb_delay * j.channels);
+    const int64_t n = j.frames * j.channels;
+    const int T = S * Ds;
+    const int TP = T + (((Ds - T) % 32) + 32) % 32;
+    const int clip0 = blockIdx.x * G;
+    const int ng = j.n_clips - clip0 < G ? j.n_clips - clip0 : G;
+    const int tid = threadIdx.x;
+    // copy lanes: rows of W lanes (a whole row of lanes when the tile is short)
+    const int wsh = T >= 256 ? 8 : 6, W = 1 << wsh, ci = tid & (W - 1), cr = tid >> wsh, crn = 256 >> wsh;
+    const bool chain = tid < ng * Ds;
+    const int g = tid / Ds, p = tid - g * Ds;
+    const float b0 = j.comb_coef[0], bd = j.comb_coef[1], ad = j.comb_coef[2];
+    float px = 0.0f, py = 0.0f;
+    if (ST && chain) {
+        px = j.comb_hist_in[(int64_t)(clip0 + g) * 2 * Ds + p];
+        py = j.comb_hist_in[(int64_t)(clip0 + g) * 2 * Ds + Ds + p];
+    }
+    float *row = cn_lds + g * TP + p;
+    for (int64_t t0 = 0; t0 < n; t0 += T) {
+        const int tn = n - t0 < T ? (int)(n - t0) : T;   // samples of this tile
+        for (int r = cr; r < ng; r += crn) {
+            gcf *x = (gcf *)j.in_ptrs[clip0 + r] + t0;
+#pragma unroll 4
+            for (int i = ci; i < tn; i += W) cn_lds[r * TP + i] = x[i];
+        }
+        __syncthreads();
+        if (chain) {
+            const int ns = tn == T ? S : (p < tn ? (tn - p - 1) / Ds + 1 : 0);
+            int s = 0;
+            for (; s + 8 <= ns; s += 8) {
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = row[(s + u) * Ds];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = comb_step(v[u], px, py, b0, bd, ad);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) row[(s + u) * Ds] = v[u];
+            }
+            for (; s < ns; ++s) row[s * Ds] = comb_step(row[s * Ds], px, py, b0, bd, ad);
+        }
+        __syncthreads();
+        for (int r = cr; r < ng; r += crn) {
+            gf *y = (gf *)j.out_ptrs[clip0 + r] + t0;
+#pragma unroll 4
+            for (int i = ci; i < tn; i += W) y[i] = cn_lds[r * TP + i];
+        }
+        __syncthreads();   // the next tile's loads overwrite the rows
+    }
+    if (ST && chain) {
+        int q = p - (int)(n % Ds);
+        if (q < 0) q += Ds;
+        j.comb_hist_out[(int64_t)(clip0 + g) * 2 * Ds + q] = px;
+        j.comb_hist_out[(int64_t)(clip0 + g) * 2 * Ds + Ds + q] = py;
+    }
+}
+
 // ---- synthetic PCM (twins: oracle/np_oracle.gen_*,
 // oracle/xm_oracle.c xo_gen_*) -------------------------------------------------
 XM_DEV uint64_t mix64(uint64_t z)
@@ -973,6 +1202,45 @@ extern "C" int xmg_launch_fx_fir(const XmhFxJob *j, void *stream)
     if (lds_rb > 64 * 1024 && xmg_func_lds((const void *)kr, (int)lds_rb)) return -1001;
     hipLaunchKernelGGL(kr, dim3((unsigned)((j->frames + FR_TILE - 1) / FR_TILE), (unsigned)j->n_clips),
                        64 * FR_WAVES, lds_rb, (hipStream_t)stream, *j);
+    return hipGetLastError() == hipSuccess ? 0 : -1001;
+}
+
+extern "C" int xmg_launch_fx_comb(const XmhFxJob *j, void *stream)
+{
+    if (j->comb_delay < 1 || j->comb_delay > (1 << 20) || (j->channels != 1 && j->channels != 2)) return -22;
+    if (!j->comb_hist_in != !j->comb_hist_out || (j->comb_hist_in && j->comb_hist_in == j->comb_hist_out)) return -22;
+    if (j->n_clips == 0 || j->frames == 0) return 0;
+    const int64_t Ds = j->comb_delay * j->channels;
+    const bool st = j->comb_hist_in != nullptr;
+    // dev knob XM_COMB_WIDE_MIN=samples (1..257): the regime switch, for the
+    // measurement that chose XMG_COMB_WIDE_MIN
+    static const int wide_min = [] {
+        const char *e = getenv("XM_COMB_WIDE_MIN");
+        const int v = e ? atoi(e) : 0;
+        return v >= 1 && v <= 257 ? v : XMG_COMB_WIDE_MIN;
+    }();
+    XmhFxJob jj = *j;
+    if (Ds >= wide_min) {
+        // 4 positions per lane once that still fills the CUs' lane slots
+        // (2048 per CU), one per lane below: more lanes, more loads in flight
+        const bool v4 = (Ds / 4) * (int64_t)j->n_clips >= (int64_t)xmg_cu_count() * 2048;
+        const int V = v4 ? 4 : 1;
+        const dim3 grid((unsigned)(((Ds + V - 1) / V + 255) / 256), (unsigned)std::min(j->n_clips, 65535));
+        auto kw = v4 ? (st ? k_comb_wide<4, 4, true> : k_comb_wide<4, 4, false>)
+                     : (st ? k_comb_wide<1, 8, true> : k_comb_wide<1, 8, false>);
+        hipLaunchKernelGGL(kw, grid, dim3(256), 0, (hipStream_t)stream, jj);
+        return hipGetLastError() == hipSuccess ? 0 : -1001;
+    }
+    // clips per workgroup: one until the grid passes 8 workgroups per CU
+    // (all resident: 256 lanes and at most 24 KiB of LDS each)
+    const int gmax = std::min(CN_MAXG, 256 / (int)Ds);
+    const int wgs = std::max(1, xmg_cu_count()) * 8;
+    const int G = std::max(1, std::min(gmax, (j->n_clips + wgs - 1) / wgs));
+    const int S = CN_TILE / (G * (int)Ds);   // >= 16: G * Ds <= 256
+    const int T = S * (int)Ds, TP = T + (((int)Ds - T) % 32 + 32) % 32;
+    const size_t lds = (size_t)G * TP * sizeof(float);   // <= (4096 + 64 * 31) * 4 B
+    auto kn = st ? k_comb_narrow<true> : k_comb_narrow<false>;
+    hipLaunchKernelGGL(kn, dim3((unsigned)((j->n_clips + G - 1) / G)), dim3(256), lds, (hipStream_t)stream, jj, G, S);
     return hipGetLastError() == hipSuccess ? 0 : -1001;
 }
 

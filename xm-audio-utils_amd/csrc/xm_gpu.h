@@ -34,6 +34,10 @@ int xmg_launch_mix_d2(const XmhMixJob *j, void *stream, int *n_launches, int *R_
 int xmg_d2_table_check(const float *H, int L, int M, int T);
 int xmg_launch_fx_biquad(const XmhFxJob *j, void *stream);                        /* xm_fx.hip */
 int xmg_launch_fx_fir(const XmhFxJob *j, void *stream);
+/* comb stage: k_comb_wide for Ds = delay * channels >= XMG_COMB_WIDE_MIN
+ * samples, k_comb_narrow below */
+#define XMG_COMB_WIDE_MIN 256
+int xmg_launch_fx_comb(const XmhFxJob *j, void *stream);
 int xmg_synth(void *out, int fmt, uint64_t seed, uint64_t clip0, int64_t n_clips, int channels, int64_t frames,
               void *stream);
 

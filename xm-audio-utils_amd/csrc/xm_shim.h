@@ -125,6 +125,18 @@ typedef struct XmhFxJob {
     float *state;
     const float *hist_in;
     float *hist_out;
+    /* comb stage (n_sos == 0, fir_len == 0, comb_delay > 0; include/xm_effects.h):
+     * y[i] = b0*x[i] + (bd*x[i-Ds] - ad*y[i-Ds]) on the interleaved samples,
+     * Ds = comb_delay * channels, comb_coef = {b0, bd, ad} by value; in == out
+     * allowed.  Streaming: comb_hist_in[clip][2][D][channel] = the last D
+     * frames of the stage's input, then of its output, before this block (NULL
+     * for whole clips: both zero); comb_hist_out (!= comb_hist_in) gets the
+     * same for the next block. */
+    int64_t comb_delay;
+    float comb_coef[3];
+    int32_t reserved3;
+    const float *comb_hist_in;
+    float *comb_hist_out;
 } XmhFxJob;
 
 /* ---------- runtime --------------------------------------------------------- */

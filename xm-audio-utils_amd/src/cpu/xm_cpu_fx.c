@@ -12,6 +12,9 @@
  *  - FIR: lanes are 16 consecutive output samples of one clip (both channels
  *    of interleaved stereo ride along: tap t reads C*t samples back), each the
  *    chain acc = +0; acc = acc + x[n-K+1+t]*h[K-1-t] over t ascending.
+ *  - Comb: y[i] = b0*x[i] + (bd*x[i-Ds] - ad*y[i-Ds]); the Ds positions of a
+ *    block of Ds samples are independent chains, so the lanes are 16
+ *    consecutive samples of one block, a block at a time.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -196,6 +199,73 @@ static void item_fir_hist(void *vctx, int64_t k)
     }
 }
 
+/* ---- comb ---------------------------------------------------------------- */
+typedef struct {
+    const XmhFxJob *j;
+    int rc;
+} CombCtx;
+
+/* one block of n <= Ds samples: y = b0*x + (bd*px - ad*py), every operation
+ * separately rounded; px, py (the previous block's x and y) become this
+ * block's.  x == y allowed: x[i] is read before y[i] is written. */
+XMC_SIMD static void comb_block(const float *x, float *y, float *restrict px, float *restrict py, int64_t n, float b0,
+                                float bd, float ad)
+{
+    int64_t i = 0;
+    for (; i + VW <= n; i += VW) {
+        const v16f xv = *(const v16fu *)(x + i);
+        const v16f p = b0 * xv, q = bd * *(const v16fu *)(px + i), r = ad * *(const v16fu *)(py + i);
+        const v16f t = q - r;
+        const v16f o = p + t;
+        *(v16fu *)(px + i) = xv;
+        *(v16fu *)(py + i) = o;
+        *(v16fu *)(y + i) = o;
+    }
+    for (; i < n; ++i) {
+        const float xv = x[i];
+        const float p = b0 * xv, q = bd * px[i], r = ad * py[i];
+        const float t = q - r;
+        const float o = p + t;
+        px[i] = xv;
+        py[i] = o;
+        y[i] = o;
+    }
+}
+
+/* One clip: position p of [0, Ds) is a chain over the blocks of Ds samples,
+ * so the lanes run along consecutive samples of a block (for Ds < 16 fewer
+ * lanes are live).  px / py hold the previous block; after the last block
+ * they are, rotated, the history of the next streaming call. */
+static void item_comb(void *vctx, int64_t k)
+{
+    CombCtx *cc = vctx;
+    const XmhFxJob *j = cc->j;
+    const int64_t Ds = j->comb_delay * j->channels, n = j->frames * j->channels;
+    float *px = malloc(sizeof(float) * 2 * (size_t)Ds), *py = px + Ds;
+    if (!px) {
+        __atomic_store_n(&cc->rc, XM_ENOMEM_, __ATOMIC_RELAXED);   /* items run on pool threads */
+        return;
+    }
+    if (j->comb_hist_in) memcpy(px, j->comb_hist_in + k * 2 * Ds, sizeof(float) * 2 * (size_t)Ds);
+    else memset(px, 0, sizeof(float) * 2 * (size_t)Ds);
+    const float *x = j->in_ptrs[k];
+    float *y = j->out_ptrs[k];
+    for (int64_t s = 0; s < n; s += Ds)
+        comb_block(x + s, y + s, px, py, n - s < Ds ? n - s : Ds, j->comb_coef[0], j->comb_coef[1], j->comb_coef[2]);
+    if (j->comb_hist_out) {
+        /* position p holds the chain's latest sample: slot (p - n) mod Ds of
+         * the last Ds samples of (history ++ block) */
+        float *hx = j->comb_hist_out + k * 2 * Ds, *hy = hx + Ds;
+        const int64_t sh = n % Ds;
+        for (int64_t p = 0; p < Ds; ++p) {
+            const int64_t q = p >= sh ? p - sh : p - sh + Ds;
+            hx[q] = px[p];
+            hy[q] = py[p];
+        }
+    }
+    free(px);
+}
+
 int xmc_launch_fx(const XmhFxJob *j, void *stream, int *n_launches)
 {
     (void)stream;
@@ -219,6 +289,12 @@ int xmc_launch_fx(const XmhFxJob *j, void *stream, int *n_launches)
             HistCtx hc = {j};
             rc = xmc_parallel(j->n_clips, item_fir_hist, &hc);
         }
+    } else if (j->comb_delay > 0) {
+        if (!j->comb_hist_in != !j->comb_hist_out || (j->comb_hist_in && j->comb_hist_in == j->comb_hist_out))
+            return XM_EINVAL_;
+        CombCtx c = {j, 0};
+        rc = xmc_parallel(j->n_clips, item_comb, &c);
+        if (!rc) rc = c.rc;
     } else {
         return 0;
     }

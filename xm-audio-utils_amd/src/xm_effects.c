@@ -1,6 +1,7 @@
 /*
  * xm_effects.c — the xm_effects_* C API: chain construction (biquad sections,
- * RBJ EQ bands designed in fp64, FIR taps), staging and dispatch of the
+ * RBJ EQ bands designed in fp64, FIR taps, comb / delay-line stages), staging
+ * and dispatch of the
  * gfx950 effects kernels (csrc/xm_fx.hip).  Build-owned API (reference has
  * none: /root/reference/README.md:1); contract in include/xm_effects.h.
  */
@@ -14,10 +15,11 @@ struct XmEffects {
     XmEffectsConfig cfg;
     int n_effects;
     struct {
-        int kind;          /* 1 biquad section, 2 FIR */
+        int kind;          /* 1 biquad section, 2 FIR, 3 comb */
         int n;             /* taps for FIR */
-        float sos[6];
+        float sos[6];      /* comb: b0, bd, ad in sos[0..2] */
         float *fir;        /* host copy */
+        int64_t delay;     /* comb: D frames */
     } fx[XM_MAX_EFFECTS];
     XmFxStage stages[XM_MAX_EFFECTS];
     int n_stages;
@@ -31,7 +33,9 @@ struct XmEffects {
     size_t ptr_cap;
     /* streaming state (xm_effects_stream_reset): per stage, biquad
      * [clip][section][z0,z1][ch] in st[s][0]; FIR [clip][K-1][ch] history
-     * ping-ponging between st[s][0] and st[s][1] (st_cur[s] = current) */
+     * ping-ponging between st[s][0] and st[s][1] (st_cur[s] = current); comb
+     * [clip][x,y][D][ch] history (the last D frames of the stage's input and
+     * of its output), ping-ponging the same way */
     float *st[XM_MAX_EFFECTS][2];
     int st_cur[XM_MAX_EFFECTS];
     size_t st_clips;
@@ -289,7 +293,65 @@ int xm_effects_add_fir(XmEffects *e, const float *h, int K)
     return XM_OK;
 }
 
+int xm_effects_add_comb(XmEffects *e, int64_t delay_frames, float b0, float bd, float ad)
+{
+    if (!e || delay_frames < 1 || delay_frames > XM_MAX_DELAY) return XM_EINVAL;
+    if (!isfinite(b0) || !isfinite(bd) || !isfinite(ad)) return XM_EINVAL;
+    if (e->n_effects >= XM_MAX_EFFECTS) return XM_ENOMEM;
+    for (int d = 0; d < e->n_sub; ++d) {   /* multi-device: every device's chain */
+        const int rc = xm_effects_add_comb(e->sub[d], delay_frames, b0, bd, ad);
+        if (rc) {
+            drop_last(e, d);   /* every device keeps the same chain */
+            return rc;
+        }
+    }
+    e->fx[e->n_effects].kind = 3;
+    e->fx[e->n_effects].n = 0;
+    e->fx[e->n_effects].fir = NULL;
+    e->fx[e->n_effects].delay = delay_frames;
+    e->fx[e->n_effects].sos[0] = b0;
+    e->fx[e->n_effects].sos[1] = bd;
+    e->fx[e->n_effects].sos[2] = ad;
+    e->n_effects++;
+    e->dirty = 1;
+    return XM_OK;
+}
+
+/* D = llrint(delay_ms * rate / 1000) in fp64, ties to even (the default
+ * rounding mode); 0 when that is outside [1, XM_MAX_DELAY] */
+static int64_t delay_frames_of(const XmEffects *e, double delay_ms)
+{
+    const double d = delay_ms * (double)e->cfg.rate / 1000.0;
+    if (!(d >= 0.5 && d <= (double)XM_MAX_DELAY + 0.5)) return 0;   /* NaN too */
+    const long long D = llrint(d);
+    return D >= 1 && D <= XM_MAX_DELAY ? (int64_t)D : 0;
+}
+
+int xm_effects_add_echo(XmEffects *e, double delay_ms, double feedback, double wet)
+{
+    if (!e) return XM_EINVAL;
+    const int64_t D = delay_frames_of(e, delay_ms);
+    if (!D) return XM_EINVAL;
+    return xm_effects_add_comb(e, D, 1.0f, (float)wet, -(float)feedback);
+}
+
+int xm_effects_add_allpass(XmEffects *e, double delay_ms, double g)
+{
+    if (!e) return XM_EINVAL;
+    const int64_t D = delay_frames_of(e, delay_ms);
+    if (!D) return XM_EINVAL;
+    return xm_effects_add_comb(e, D, -(float)g, 1.0f, -(float)g);
+}
+
 int xm_effects_count(const XmEffects *e) { return e ? e->n_effects : XM_EINVAL; }
+
+int xm_effects_get_comb(const XmEffects *e, int i, int64_t *delay_frames, float coef[3])
+{
+    if (!e || !delay_frames || !coef || i < 0 || i >= e->n_effects || e->fx[i].kind != 3) return XM_EINVAL;
+    *delay_frames = e->fx[i].delay;
+    memcpy(coef, e->fx[i].sos, sizeof(float) * 3);
+    return XM_OK;
+}
 
 int xm_effects_get_biquad(const XmEffects *e, int i, float sos[6])
 {
@@ -317,16 +379,19 @@ XmEffects *xm_effects_clone_on(const XmEffects *src, int device, int *status)
     c.device = device;
     int rc = XM_OK;
     XmEffects *e = xm_effects_create_ex(&c, &rc);
-    for (int i = 0; e && !rc && i < src->n_effects; ++i)
-        rc = src->fx[i].kind == 1 ? xm_effects_add_biquad(e, src->fx[i].sos)
-                                  : xm_effects_add_fir(e, src->fx[i].fir, src->fx[i].n);
+    for (int i = 0; e && !rc && i < src->n_effects; ++i) {
+        if (src->fx[i].kind == 1) rc = xm_effects_add_biquad(e, src->fx[i].sos);
+        else if (src->fx[i].kind == 2) rc = xm_effects_add_fir(e, src->fx[i].fir, src->fx[i].n);
+        else rc = xm_effects_add_comb(e, src->fx[i].delay, src->fx[i].sos[0], src->fx[i].sos[1], src->fx[i].sos[2]);
+    }
     if (rc) xm_effects_freep(&e);
     if (status) *status = rc;
     return e;
 }
 
 /* Group consecutive biquads into cascades (<= XM_MAX_SOS sections each) and
- * upload coefficients. */
+ * upload coefficients.  A comb is a stage of its own (no device buffer: its
+ * coefficients travel in the job). */
 static int build_stages(XmEffects *e)
 {
     if (!e->dirty) return XM_OK;
@@ -347,6 +412,13 @@ static int build_stages(XmEffects *e)
             s->n = n;
             rc = xmh_malloc((void **)&s->coef_dev, sizeof(float) * 6 * (size_t)n);
             if (!rc) rc = xmh_memcpy_h2d(s->coef_dev, buf, sizeof(float) * 6 * (size_t)n, e->stream);
+        } else if (e->fx[i].kind == 3) {
+            s->kind = 3;
+            s->n = 0;
+            s->coef_dev = NULL;
+            s->delay = e->fx[i].delay;
+            memcpy(s->comb, e->fx[i].sos, sizeof(float) * 3);
+            ++i;
         } else {
             s->kind = 2;
             s->n = e->fx[i].n;
@@ -440,7 +512,9 @@ static int run_chain(XmEffects *e, size_t batch, size_t frames, float **src, flo
     /* FIR reads neighbours of the samples it writes: never run it in place.
      * If any clip is processed in place and the chain has a FIR stage, first
      * copy the inputs to buf0.  A biquad cascade runs in place (each chunk is
-     * read into LDS before its outputs are stored). */
+     * read into LDS before its outputs are stored), and so does a comb (the
+     * owner of a sample reads it before it writes it): both take whatever
+     * (cur, nxt) pair the FIR bookkeeping hands them, equal or not. */
     int inplace = 0, off = 0, has_fir = 0;
     for (int s = 0; s < e->n_stages; ++s) has_fir |= e->stages[s].kind == 2;
     for (size_t i = 0; has_fir && i < batch; ++i) inplace |= src[i] == dst[i];
@@ -466,6 +540,14 @@ static int run_chain(XmEffects *e, size_t batch, size_t frames, float **src, flo
             j.sos = e->stages[s].coef_dev;
             j.n_sos = e->stages[s].n;
             if (streaming) j.state = e->st[s][0] + clip0 * (size_t)j.n_sos * 2 * C2;
+        } else if (e->stages[s].kind == 3) {
+            j.comb_delay = e->stages[s].delay;
+            memcpy(j.comb_coef, e->stages[s].comb, sizeof(float) * 3);
+            if (streaming) {
+                const size_t hoff = clip0 * 2 * (size_t)j.comb_delay * C2;
+                j.comb_hist_in = e->st[s][e->st_cur[s]] + hoff;
+                j.comb_hist_out = e->st[s][e->st_cur[s] ^ 1] + hoff;
+            }
         } else {
             j.fir = e->stages[s].coef_dev;
             j.fir_len = e->stages[s].n;
@@ -589,8 +671,9 @@ int xm_effects_stream_reset(XmEffects *e, size_t n_clips)
     free_stream_state(e);
     const size_t C = (size_t)e->cfg.channels;
     for (int s = 0; !rc && s < e->n_stages; ++s) {
-        const size_t per = e->stages[s].kind == 1 ? (size_t)e->stages[s].n * 2 * C
-                                                   : (size_t)(e->stages[s].n - 1) * C;
+        const size_t per = e->stages[s].kind == 1   ? (size_t)e->stages[s].n * 2 * C
+                           : e->stages[s].kind == 3 ? 2 * (size_t)e->stages[s].delay * C
+                                                    : (size_t)(e->stages[s].n - 1) * C;
         if (per == 0) continue;   /* 1-tap FIR: no history */
         const size_t bytes = n_clips * per * sizeof(float);
         const int nbuf = e->stages[s].kind == 1 ? 1 : 2;
@@ -625,6 +708,6 @@ int xm_effects_process_stream(XmEffects *e, const float *const *in, float *const
     rc = process(e, in, out, n_clips, frames, 1);
     if (!rc)
         for (int s = 0; s < e->n_stages; ++s)
-            if (e->stages[s].kind == 2) e->st_cur[s] ^= 1;   /* hist_out becomes the history */
+            if (e->stages[s].kind != 1) e->st_cur[s] ^= 1;   /* hist_out becomes the history */
     return rc;
 }

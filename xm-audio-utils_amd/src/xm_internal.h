@@ -29,9 +29,11 @@ int xm_gain_to_dev(const XmGainRamp *g, XmhGain *d);
 
 /* Effects chain internals (used by the mixer for per-track chains). */
 typedef struct XmFxStage {
-    int kind;              /* 1 = biquad cascade, 2 = FIR */
+    int kind;              /* 1 = biquad cascade, 2 = FIR, 3 = comb */
     int n;                 /* sections or taps */
-    float *coef_dev;       /* n*6 (biquad) or n (FIR) floats on device */
+    float *coef_dev;       /* n*6 (biquad) or n (FIR) floats on device; comb: NULL */
+    int64_t delay;         /* comb: D frames */
+    float comb[3];         /* comb: b0, bd, ad (travel by value in the job) */
 } XmFxStage;
 
 int xm_effects_stages(const XmEffects *e, const XmFxStage **stages, int *n_stages);

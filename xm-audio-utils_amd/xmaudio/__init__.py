@@ -44,6 +44,7 @@ XM_MIXER_OUT_CONVERT = 1
 XM_MIXER_IN_CONVERT = 2
 XM_MIXER_PLANAR = 4
 XM_GAIN_RAMP, XM_GAIN_XFADE_OUT = 0, 1
+XM_MAX_DELAY = 1 << 20   # comb stages: frames (include/xm_effects.h)
 XM_EQ_PEAKING, XM_EQ_LOWSHELF, XM_EQ_HIGHSHELF, XM_EQ_LOWPASS, XM_EQ_HIGHPASS = range(5)
 FMT = {"s16": XM_FMT_S16, "f32": XM_FMT_F32}
 DTYPE = {XM_FMT_S16: np.int16, XM_FMT_F32: np.float32}
@@ -67,6 +68,7 @@ EXPORTED = [
     "xm_audio_mixer_create_multi", "xm_audio_mixer_n_devices", "xm_audio_mixer_process_sharded",
     "xm_audio_mixer_mix_spanning_s16", "xm_effects_create_multi", "xm_effects_n_devices",
     "xm_audio_mixer_last_fast_split", "xm_audio_mixer_set_span_chunks",
+    "xm_effects_add_comb", "xm_effects_add_echo", "xm_effects_add_allpass", "xm_effects_get_comb",
 ]
 
 
@@ -151,6 +153,10 @@ _sigs = {
     "xm_effects_n_devices": (_i, [_vp]),
     "xm_audio_mixer_last_fast_split": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "xm_audio_mixer_set_span_chunks": (_i, [_vp, _i]),
+    "xm_effects_add_comb": (_i, [_vp, _i64, C.c_float, C.c_float, C.c_float]),
+    "xm_effects_add_echo": (_i, [_vp, C.c_double, C.c_double, C.c_double]),
+    "xm_effects_add_allpass": (_i, [_vp, C.c_double, C.c_double]),
+    "xm_effects_get_comb": (_i, [_vp, _i, C.POINTER(_i64), C.POINTER(C.c_float)]),
 }
 for _n, (_r, _a) in _sigs.items():
     if os.environ.get("XM_AUDIO_LIB") and not hasattr(_lib, _n):
@@ -473,8 +479,24 @@ class Effects:
         h = np.ascontiguousarray(h, np.float32)
         _check(_lib.xm_effects_add_fir(self._h, h.ctypes.data_as(C.POINTER(C.c_float)), len(h)), "add_fir")
 
+    def add_comb(self, delay_frames: int, b0: float, bd: float, ad: float):
+        """y[n] = b0*x[n] + (bd*x[n-D] - ad*y[n-D]) per channel, D = delay_frames."""
+        _check(_lib.xm_effects_add_comb(self._h, delay_frames, b0, bd, ad), "add_comb")
+
+    def add_echo(self, delay_ms: float, feedback: float, wet: float):
+        _check(_lib.xm_effects_add_echo(self._h, delay_ms, feedback, wet), "add_echo")
+
+    def add_allpass(self, delay_ms: float, g: float):
+        _check(_lib.xm_effects_add_allpass(self._h, delay_ms, g), "add_allpass")
+
     def count(self) -> int:
         return _lib.xm_effects_count(self._h)
+
+    def comb(self, i: int):
+        """(delay_frames, [b0, bd, ad] float32) of comb effect i."""
+        d, c = _i64(0), (C.c_float * 3)()
+        _check(_lib.xm_effects_get_comb(self._h, i, C.byref(d), c), "get_comb")
+        return d.value, np.array(c[:], np.float32)
 
     def biquad(self, i: int) -> np.ndarray:
         s = (C.c_float * 6)()
