@@ -1,5 +1,5 @@
 /*
- * xm_effects.h — biquad / FIR / comb effects chain over batches of clips (C ABI).
+ * xm_effects.h — biquad / FIR / comb / comb-bank effects chain over batches of clips (C ABI).
  *
  * BUILD-OWNED ABI (reference has no headers: /root/reference/README.md:1;
  * prefix xm_effects_* from BASELINE.json:5, signatures from SURVEY.md §8(b)).
@@ -24,8 +24,22 @@
  *  part of the contract.
  *  (scipy lfilter(b, a, x) in float32 with b = [b0, 0, ..., bd] and
  *  a = [1, 0, ..., ad], both of length D+1)
+ *  comb bank (parallel combs: the body of a Schroeder reverberator) of n
+ *  branches (D_k, b0_k, bd_k, ad_k, mix_k) and a dry weight, per clip on the
+ *  interleaved sample stream with lags Ds_k = D_k*C, so channels never mix.
+ *  Branch k is exactly the comb above, applied to the stage's input x:
+ *      c_k[i] = b0_k*x[i] + ( bd_k*x[i-Ds_k] - ad_k*c_k[i-Ds_k] )
+ *  (the same five separately rounded operations, zero history before the
+ *  clip, denormals kept, signed zeros as computed; every product is formed,
+ *  also one with a zero coefficient), and the output sums the branches in
+ *  ascending order:
+ *      acc = dry*x[i];  for k = 0 .. n-1:  m = mix_k*c_k[i];  acc = acc + m
+ *      y[i] = acc
+ *  every multiply and add rounded to fp32 separately, no contraction.
+ *  (c_k = scipy lfilter in float32 as above; the sum in the order written)
  *  Effects run in insertion order; consecutive biquads form one cascade; a
- *  comb is a stage of its own and never merges with its neighbours.
+ *  comb and a comb bank are stages of their own and never merge with their
+ *  neighbours.
  */
 #ifndef XM_EFFECTS_H
 #define XM_EFFECTS_H
@@ -107,11 +121,40 @@ XM_API int xm_effects_add_echo(XmEffects *e, double delay_ms, double feedback, d
  * -(float)g, 1, -(float)g), D as for add_echo. */
 XM_API int xm_effects_add_allpass(XmEffects *e, double delay_ms, double g);
 
+/* Comb bank (the arithmetic above): n combs in parallel on the stage's input,
+ * summed with weights mix_k onto dry*x.  1 <= n <= XM_MAX_BANK, every delay in
+ * [1, XM_MAX_DELAY], every coefficient and dry finite (XM_EINVAL otherwise;
+ * XM_ENOMEM beyond 128 effects).  Equal lags in several branches are legal;
+ * stability is not checked.  taps is copied. */
+#define XM_MAX_BANK 8
+typedef struct XmCombTap {
+    int64_t delay_frames;   /* 1 .. XM_MAX_DELAY */
+    float b0, bd, ad;       /* the comb stage's coefficients */
+    float mix;              /* weight of this branch in the sum */
+} XmCombTap;
+XM_API int xm_effects_add_comb_bank(XmEffects *e, const XmCombTap *taps, int n, float dry);
+
+/* Schroeder reverberator: appends three effects, all or none.  A bank of four
+ * feedback combs of 29.7, 37.1, 41.1 and 43.7 ms (D_k = llrint(ms * rate /
+ * 1000.0), as add_echo), each b0 = 0, bd = 1, ad = -(float)pow(10.0,
+ * -3.0 * D_k / (rate * rt60_s)) (the loop gain that decays by 60 dB in
+ * rt60_s seconds), mix = (float)wet, the bank's dry = (float)dry; then
+ * add_allpass(5.0 ms, 0.7) and add_allpass(1.7 ms, 0.7).  XM_EINVAL unless
+ * rt60_s is finite and > 0, dry and wet are finite and every delay rounds into
+ * [1, XM_MAX_DELAY]; XM_ENOMEM when the chain has no room for three effects.
+ * The dry signal passes the two all-passes too (their magnitude response is
+ * flat, their phase is not): for an untouched dry path run the reverb with
+ * dry = 0 on a send track and sum it with the dry track in the mixer. */
+XM_API int xm_effects_add_reverb(XmEffects *e, double rt60_s, double dry, double wet);
+
 /* Number of effects and the coefficients of biquad i (for inspection). */
 XM_API int xm_effects_count(const XmEffects *e);
 XM_API int xm_effects_get_biquad(const XmEffects *e, int index, float sos[6]);
 /* Delay and coef = {b0, bd, ad} of comb i; XM_EINVAL when effect i is not a comb. */
 XM_API int xm_effects_get_comb(const XmEffects *e, int index, int64_t *delay_frames, float coef[3]);
+/* Taps, their number and the dry weight of comb bank i; XM_EINVAL when effect
+ * i is not a bank (get_comb on a bank returns XM_EINVAL as well). */
+XM_API int xm_effects_get_comb_bank(const XmEffects *e, int index, XmCombTap taps[XM_MAX_BANK], int *n, float *dry);
 
 /* Install a caller-owned hipStream_t (NULL: the chain's own stream, which is
  * created blocking: ordered after the legacy default stream's work, as a
@@ -128,8 +171,9 @@ XM_API int xm_effects_process_batch(XmEffects *e, const float *const *in, float 
  * xm_effects_process_stream() call filters the next `frames` frames of each
  * stream (in[i] / out[i] as process_batch, in == out allowed), carrying on
  * the device the biquad state (z0, z1 per section and channel), the last
- * K-1 input frames of every FIR stage and the last D input and D output
- * frames of every comb stage.  Any split of a signal into blocks (ragged,
+ * K-1 input frames of every FIR stage, the last D input and D output
+ * frames of every comb stage and, of every comb bank, the last D_k output
+ * frames of each branch and the last max D_k input frames.  Any split of a signal into blocks (ragged,
  * 1-frame or empty blocks, longer or shorter than D) gives, bit for bit, the output of one
  * process_batch() over the whole signal.  Adding an effect ends the streams:
  * process_stream then fails with XM_EINVAL until the next reset, as it does

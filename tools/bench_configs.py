@@ -26,6 +26,10 @@ stream  the headline pushed in 8 blocks through stream_push (fused bulk straight
 oconv   the headline with XM_MIXER_OUT_CONVERT: s16 output (fused kernel epilogue)
 comb    comb stage alone, D = 11025 frames (250 ms echo), 1024 stereo 10 s fp32 clips in place (k_comb_wide)
 comb1   the same with D = 1 (k_comb_narrow); both report vs_copy against a torch device copy of the same bytes
+bank4   comb bank alone (k_bank), the reverb preset's four combs of 29.7-43.7 ms, the same clips in place, delay lines in LDS
+bank8   eight branches of 25-45 ms with b0 and bd live, still in LDS
+bankfar four branches of 200-350 ms, delay lines in device scratch; the three report vs_copy and vs_serial
+        (time over N x the single comb stage at the bank's median lag), each the minimum of three timings
 Unit: input samples (frames x channels x tracks) per second; roofline
 fraction = algorithmic bytes (inputs once + output once) / kernel time / 8 TB/s.
 Inputs are synthetic PCM generated in HBM (xm_synth_pcm), outside the timing.
@@ -394,6 +398,80 @@ def _comb(a, name, D):
             "workload": f"comb D={D} (echo), {B} stereo 10 s fp32 clips @ 44.1 kHz, in place",
             "value": round(B * N * 2 / (w * 1e-3) / 1e6, 1), "unit": "Msamples/s", "ms_per_step": round(w, 4),
             "kernel_ms": round(k, 4), "copy_ms": round(kc, 4), "vs_copy": round(k / kc, 3),
+            "roofline": {"bound": "hbm", "alg_bytes": alg, "achieved_GBps": round(alg / (k * 1e-3) / 1e9, 1),
+                         "frac": round(alg / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+            "parity": ok, "parity_check": ok}
+    print(json.dumps(line), flush=True)
+
+
+def _bank_taps(ms, b0, bd):
+    """Feedback combs of the given delays at 44.1 kHz with loop gains of a 1.8 s decay, equal weights."""
+    out = []
+    for m in ms:
+        D = int(np.rint(m * 44100 / 1000.0))
+        out.append((D, b0, bd, -float(np.float32(10.0 ** (-3.0 * D / (44100 * 1.8)))), 1.0 / len(ms)))
+    return out
+
+
+def bank4(a):   # the reverb preset's bank alone (delay lines in LDS)
+    _bank(a, "bank4", _bank_taps((29.7, 37.1, 41.1, 43.7), 0.0, 1.0), 0.7)
+
+
+def bank8(a):   # eight branches of 25-45 ms, b0 and bd live (still in LDS)
+    _bank(a, "bank8", _bank_taps((25.0, 27.9, 30.7, 33.6, 36.4, 39.3, 42.1, 45.0), 0.25, 0.75), 0.7)
+
+
+def bankfar(a):   # four branches of 200-350 ms: delay lines in device scratch
+    _bank(a, "bankfar", _bank_taps((200.0, 250.0, 300.0, 350.0), 0.0, 1.0), 0.7)
+
+
+def _bank(a, name, taps, dry):
+    """Comb bank alone over 1024 stereo 10 s clips @ 44.1 kHz, device memory, in
+    place, the minimum of three timings.  vs_copy = that over a torch
+    device-to-device copy of the same bytes; vs_serial = that over N times the
+    single comb stage at the bank's median lag on the same clips (N passes are
+    the least an unfused route costs, before its summing passes), each the
+    minimum of three timings in this process."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from bank_ref import bank_f32
+    B, N = a.clips_fx, 441000
+    e = xm.Effects(44100, 2, mem="device")
+    e.add_comb_bank(taps, dry)
+    rtaps, rdry = e.comb_bank(0)
+    dmed = int(np.median([t[0] for t in taps]))
+    ec = xm.Effects(44100, 2, mem="device")
+    ec.add_comb(dmed, 0.0, 1.0, taps[0][3])
+    x = torch.empty((B, N, 2), dtype=torch.float32, device="cuda")
+    s = torch.cuda.current_stream()
+    synth = lambda: xm.synth(x.data_ptr(), "f32", SEED, 0, B, 2, N, 0, s.cuda_stream)
+    synth()
+    x0 = x[ends(B)].clone()
+    e.set_stream(s.cuda_stream)
+    ec.set_stream(s.cuda_stream)
+    ptrs = [x[b].data_ptr() for b in range(B)]
+    # one checked pass, then timed passes (in place: each pass filters the previous output)
+    e.process_ptrs(ptrs, ptrs, N)
+    torch.cuda.synchronize()
+    ok = parity(a, lambda: all(beq(x[b].cpu().numpy(), bank_f32(x0[i].cpu().numpy(), rtaps, rdry))
+                               for i, b in enumerate(ends(B))))
+    y = torch.empty_like(x)
+    ks, kss, kcs, w = [], [], [], 0.0
+    for _ in range(3):   # every timing starts from bounded input again
+        synth()
+        w, k = timed(lambda: e.process_ptrs(ptrs, ptrs, N), a.steps, a.warmup, s)
+        ks.append(k)
+        synth()
+        kss.append(timed(lambda: ec.process_ptrs(ptrs, ptrs, N), a.steps, a.warmup, s)[1])
+        kcs.append(timed(lambda: y.copy_(x), a.steps, a.warmup, s)[1])
+    k, ksingle, kc = min(ks), min(kss), min(kcs)
+    alg = 2 * B * N * 2 * 4
+    line = {"config": name, "delays_frames": [t[0] for t in taps], "branches": len(taps),
+            "workload": f"comb bank of {len(taps)}, {B} stereo 10 s fp32 clips @ 44.1 kHz, in place",
+            "value": round(B * N * 2 / (k * 1e-3) / 1e6, 1), "unit": "Msamples/s", "ms_per_step": round(w, 4),
+            "kernel_ms": round(k, 4), "kernel_ms_all": [round(v, 4) for v in ks],
+            "copy_ms": round(kc, 4), "vs_copy": round(k / kc, 3),
+            "single_comb_ms": round(ksingle, 4), "single_comb_delay": dmed,
+            "vs_serial": round(k / (len(taps) * ksingle), 3),
             "roofline": {"bound": "hbm", "alg_bytes": alg, "achieved_GBps": round(alg / (k * 1e-3) / 1e9, 1),
                          "frac": round(alg / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "parity": ok, "parity_check": ok}

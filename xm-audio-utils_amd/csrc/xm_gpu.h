@@ -38,6 +38,9 @@ int xmg_launch_fx_fir(const XmhFxJob *j, void *stream);
  * samples, k_comb_narrow below */
 #define XMG_COMB_WIDE_MIN 256
 int xmg_launch_fx_comb(const XmhFxJob *j, void *stream);
+/* comb bank (xm_fx_bank.hip): delay lines in LDS up to XMH_BANK_LDS_FLOATS
+ * samples per clip, in job->bank_scratch beyond */
+int xmg_launch_fx_bank(const XmhFxJob *j, void *stream);
 int xmg_synth(void *out, int fmt, uint64_t seed, uint64_t clip0, int64_t n_clips, int channels, int64_t frames,
               void *stream);
 

@@ -104,6 +104,15 @@ typedef struct XmhMixJob {
 #define XMH_IO_OUT_PLANAR 4   /* mix output = C planes of frames_out samples */
 
 /* ---------- effects job ---------------------------------------------------- */
+#define XMH_MAX_BANK 8              /* XM_MAX_BANK (include/xm_effects.h) */
+#define XMH_BANK_BLOCK 2048         /* samples of a clip that a bank workgroup filters between two barriers, at most */
+#define XMH_BANK_LDS_FLOATS 40960   /* delay lines of a clip up to this many samples (160 KiB) stay in LDS */
+#define XMH_BANK_SCRATCH_SLOTS 512  /* workgroups of a bank launch whose delay lines live in device scratch, at most */
+typedef struct XmhBankTap {
+    int64_t delay;                  /* D frames */
+    float b0, bd, ad, mix;
+} XmhBankTap;
+
 typedef struct XmhFxJob {
     int32_t channels;
     int32_t n_clips;
@@ -137,7 +146,43 @@ typedef struct XmhFxJob {
     int32_t reserved3;
     const float *comb_hist_in;
     float *comb_hist_out;
+    /* comb bank (n_sos == 0, fir_len == 0, comb_delay == 0, bank_n > 0;
+     * include/xm_effects.h): bank_n combs in parallel on the stage's input,
+     * y[i] = dry*x[i] + mix_0*c_0[i] + ... in ascending order, taps by value;
+     * in == out allowed.  Streaming: bank_hist_in[clip] = the last D_k frames
+     * of c_k for k = 0 .. bank_n-1, then the last max D_k frames of the
+     * stage's input, oldest first (xmh_bank_hist_floats floats per clip; NULL
+     * for whole clips: all zero); bank_hist_out (!= bank_hist_in) gets the same
+     * for the next block.  bank_scratch: device memory for the delay lines
+     * when they exceed XMH_BANK_LDS_FLOATS per clip (the GPU backend; the CPU
+     * backend ignores it): bank_scratch_slots x xmh_bank_ring_floats floats,
+     * one slot per workgroup. */
+    int32_t bank_n;
+    float bank_dry;
+    XmhBankTap bank_taps[XMH_MAX_BANK];
+    const float *bank_hist_in;
+    float *bank_hist_out;
+    float *bank_scratch;
+    int32_t bank_scratch_slots;
+    int32_t reserved4;
 } XmhFxJob;
+
+/* samples of the streaming history of one clip: every branch's output line, then the input line */
+static inline int64_t xmh_bank_hist_floats(const XmhFxJob *j)
+{
+    int64_t sum = 0, mx = 0;
+    for (int k = 0; k < j->bank_n; ++k) {
+        const int64_t Ds = j->bank_taps[k].delay * j->channels;
+        sum += Ds;
+        if (Ds > mx) mx = Ds;
+    }
+    return sum + mx;
+}
+
+/* samples of the delay lines of one clip while a kernel runs: the input line
+ * is a ring one time block longer than the longest lag, so the block's own
+ * inputs never land on a slot the block still reads */
+static inline int64_t xmh_bank_ring_floats(const XmhFxJob *j) { return xmh_bank_hist_floats(j) + XMH_BANK_BLOCK; }
 
 /* ---------- runtime --------------------------------------------------------- */
 int  xmh_device_count(void);

@@ -382,6 +382,7 @@ int xmg_launch_fx(const XmhFxJob *j, void *stream, int *n_launches)
     if (j->n_sos > 0) rc = xmg_launch_fx_biquad(j, stream);
     else if (j->fir_len > 0) rc = xmg_launch_fx_fir(j, stream);
     else if (j->comb_delay > 0) rc = xmg_launch_fx_comb(j, stream);
+    else if (j->bank_n > 0) rc = xmg_launch_fx_bank(j, stream);
     else return 0;
     if (n_launches) *n_launches += 1;
     return rc;

@@ -15,6 +15,9 @@
  *  - Comb: y[i] = b0*x[i] + (bd*x[i-Ds] - ad*y[i-Ds]); the Ds positions of a
  *    block of Ds samples are independent chains, so the lanes are 16
  *    consecutive samples of one block, a block at a time.
+ *  - Comb bank: y = dry*x + mix_0*c_0 + ... with every c_k a comb on x; one
+ *    branch at a time over the whole clip into an accumulator row, so each
+ *    sample adds its branches in ascending order.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -266,6 +269,70 @@ static void item_comb(void *vctx, int64_t k)
     free(px);
 }
 
+/* ---- comb bank ----------------------------------------------------------- */
+/* One clip: acc = dry*x, then branch after branch over the whole clip, each a
+ * comb (comb_block over blocks of its own Ds_k samples) whose output joins
+ * acc as acc = acc + mix_k*c_k.  Every sample so sees its branches in
+ * ascending k, the order of the contract, and every loop runs along
+ * consecutive samples.  acc is a buffer of its own, so x stays whole until
+ * the last branch has read it (in == out allowed). */
+static void item_bank(void *vctx, int64_t k)
+{
+    CombCtx *cc = vctx;
+    const XmhFxJob *j = cc->j;
+    const int64_t C = j->channels, n = j->frames * C;
+    int64_t sum = 0, mx = 0;
+    for (int b = 0; b < j->bank_n; ++b) {
+        const int64_t Ds = j->bank_taps[b].delay * C;
+        sum += Ds;
+        mx = Ds > mx ? Ds : mx;
+    }
+    const int64_t H = sum + mx;   /* xmh_bank_hist_floats */
+    float *acc = malloc(sizeof(float) * (size_t)(n + 3 * mx));
+    if (!acc) {
+        __atomic_store_n(&cc->rc, XM_ENOMEM_, __ATOMIC_RELAXED);   /* items run on pool threads */
+        return;
+    }
+    float *cb = acc + n, *px = cb + mx, *py = px + mx;
+    const float *x = j->in_ptrs[k];
+    float *y = j->out_ptrs[k];
+    const float *hin = j->bank_hist_in ? j->bank_hist_in + k * H : NULL;
+    float *hout = j->bank_hist_out ? j->bank_hist_out + k * H : NULL;
+    const float dry = j->bank_dry;
+    for (int64_t i = 0; i < n; ++i) acc[i] = dry * x[i];
+    int64_t off = 0;
+    for (int b = 0; b < j->bank_n; ++b) {
+        const XmhBankTap *t = &j->bank_taps[b];
+        const int64_t Ds = t->delay * C;
+        if (hin) {
+            memcpy(px, hin + sum + (mx - Ds), sizeof(float) * (size_t)Ds);   /* the last Ds inputs */
+            memcpy(py, hin + off, sizeof(float) * (size_t)Ds);
+        } else {
+            memset(px, 0, sizeof(float) * (size_t)Ds);
+            memset(py, 0, sizeof(float) * (size_t)Ds);
+        }
+        const float mix = t->mix;
+        for (int64_t s = 0; s < n; s += Ds) {
+            const int64_t m = n - s < Ds ? n - s : Ds;
+            comb_block(x + s, cb, px, py, m, t->b0, t->bd, t->ad);
+            float *a = acc + s;
+            for (int64_t i = 0; i < m; ++i) {
+                const float mm = mix * cb[i];
+                a[i] = a[i] + mm;
+            }
+        }
+        if (hout) {   /* as item_comb: position p holds slot (p - n) mod Ds */
+            const int64_t sh = n % Ds;
+            for (int64_t p = 0; p < Ds; ++p) hout[off + (p >= sh ? p - sh : p - sh + Ds)] = py[p];
+        }
+        off += Ds;
+    }
+    if (hout)   /* the last mx samples of (history ++ x), before y may overwrite x */
+        for (int64_t q = 0; q < mx; ++q) hout[sum + q] = n - mx + q >= 0 ? x[n - mx + q] : hin[sum + q + n];
+    memcpy(y, acc, sizeof(float) * (size_t)n);
+    free(acc);
+}
+
 int xmc_launch_fx(const XmhFxJob *j, void *stream, int *n_launches)
 {
     (void)stream;
@@ -294,6 +361,15 @@ int xmc_launch_fx(const XmhFxJob *j, void *stream, int *n_launches)
             return XM_EINVAL_;
         CombCtx c = {j, 0};
         rc = xmc_parallel(j->n_clips, item_comb, &c);
+        if (!rc) rc = c.rc;
+    } else if (j->bank_n > 0) {
+        if (j->bank_n > XMH_MAX_BANK) return XM_EINVAL_;
+        for (int k = 0; k < j->bank_n; ++k)
+            if (j->bank_taps[k].delay < 1) return XM_EINVAL_;
+        if (!j->bank_hist_in != !j->bank_hist_out || (j->bank_hist_in && j->bank_hist_in == j->bank_hist_out))
+            return XM_EINVAL_;
+        CombCtx c = {j, 0};
+        rc = xmc_parallel(j->n_clips, item_bank, &c);
         if (!rc) rc = c.rc;
     } else {
         return 0;

@@ -696,7 +696,7 @@ static int run_with_effects(XmAudioMixer *m, const XmhMixJob *j0, int *launches)
     const size_t per_track = fx_track_stride(j0->frames_out, C);
     const size_t ntot = (size_t)j0->n_mix * (size_t)ntr;
     /* FIR stages read neighbours of what they write: they ping-pong between
-     * two track buffers; biquad cascades and combs run in place */
+     * two track buffers; biquad cascades, combs and comb banks run in place */
     const XmFxStage *st = NULL;
     int ns = 0, has_fir = 0;
     int rc = xm_effects_stages(m->fx, &st, &ns);
@@ -782,6 +782,10 @@ static int run_with_effects(XmAudioMixer *m, const XmhMixJob *j0, int *launches)
                 fj.out_ptrs = (float *const *)(tmp_ptrs + (size_t)cur * ntot);
                 fj.comb_delay = st[s].delay;
                 memcpy(fj.comb_coef, st[s].comb, sizeof fj.comb_coef);
+            } else if (st[s].kind == 4) {   /* comb bank: in place as well */
+                fj.out_ptrs = (float *const *)(tmp_ptrs + (size_t)cur * ntot);
+                rc = xm_effects_bank_job(m->fx, &st[s], &fj);
+                if (rc) break;
             } else {
                 fj.out_ptrs = (float *const *)(tmp_ptrs + (size_t)(cur ^ 1) * ntot);
                 fj.fir = st[s].coef_dev;

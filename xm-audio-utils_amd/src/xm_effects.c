@@ -1,7 +1,7 @@
 /*
  * xm_effects.c — the xm_effects_* C API: chain construction (biquad sections,
- * RBJ EQ bands designed in fp64, FIR taps, comb / delay-line stages), staging
- * and dispatch of the
+ * RBJ EQ bands designed in fp64, FIR taps, comb / delay-line stages, comb
+ * banks and the reverb preset built from them), staging and dispatch of the
  * gfx950 effects kernels (csrc/xm_fx.hip).  Build-owned API (reference has
  * none: /root/reference/README.md:1); contract in include/xm_effects.h.
  */
@@ -15,11 +15,12 @@ struct XmEffects {
     XmEffectsConfig cfg;
     int n_effects;
     struct {
-        int kind;          /* 1 biquad section, 2 FIR, 3 comb */
-        int n;             /* taps for FIR */
-        float sos[6];      /* comb: b0, bd, ad in sos[0..2] */
+        int kind;          /* 1 biquad section, 2 FIR, 3 comb, 4 comb bank */
+        int n;             /* taps for FIR, branches for a bank */
+        float sos[6];      /* comb: b0, bd, ad in sos[0..2]; bank: dry in sos[0] */
         float *fir;        /* host copy */
         int64_t delay;     /* comb: D frames */
+        XmCombTap *bank;   /* bank: host copy of the n branches */
     } fx[XM_MAX_EFFECTS];
     XmFxStage stages[XM_MAX_EFFECTS];
     int n_stages;
@@ -35,11 +36,18 @@ struct XmEffects {
      * [clip][section][z0,z1][ch] in st[s][0]; FIR [clip][K-1][ch] history
      * ping-ponging between st[s][0] and st[s][1] (st_cur[s] = current); comb
      * [clip][x,y][D][ch] history (the last D frames of the stage's input and
-     * of its output), ping-ponging the same way */
+     * of its output), ping-ponging the same way; comb bank [clip] the last
+     * D_k frames of every branch's output, k ascending, then the last max D_k
+     * frames of the stage's input (csrc/xm_shim.h bank_hist_in), ping-ponging
+     * as well */
     float *st[XM_MAX_EFFECTS][2];
     int st_cur[XM_MAX_EFFECTS];
     size_t st_clips;
     int st_ready;
+    /* delay lines of comb banks too long for the LDS (csrc/xm_fx_bank.hip):
+     * one buffer, shared by the chain's bank stages, which run in stream order */
+    void *bank_scr;
+    size_t bank_scr_cap;
     /* multi-device chain (xm_effects_create_multi / n_devices > 1): one
      * single-device chain per entry of devs, a worker thread per device
      * (src/xm_pool.c); a batch's clips are cut into contiguous blocks, block
@@ -166,7 +174,10 @@ void xm_effects_freep(XmEffects **pe)
     if (e->n_sub) {
         xm_pool_free(&e->pool);
         for (int d = 0; d < e->n_sub; ++d) xm_effects_freep(&e->sub[d]);
-        for (int i = 0; i < e->n_effects; ++i) free(e->fx[i].fir);
+        for (int i = 0; i < e->n_effects; ++i) {
+            free(e->fx[i].fir);
+            free(e->fx[i].bank);
+        }
         free(e);
         *pe = NULL;
         return;
@@ -175,7 +186,11 @@ void xm_effects_freep(XmEffects **pe)
     if (e->own_stream) xmh_stream_sync(e->own_stream);
     free_stages(e);
     free_stream_state(e);
-    for (int i = 0; i < e->n_effects; ++i) free(e->fx[i].fir);
+    for (int i = 0; i < e->n_effects; ++i) {
+        free(e->fx[i].fir);
+        free(e->fx[i].bank);
+    }
+    xmh_free(e->bank_scr);
     xmh_free(e->d_buf[0]);
     xmh_free(e->d_buf[1]);
     xmh_free(e->d_ptrs);
@@ -194,6 +209,8 @@ static void drop_last(XmEffects *e, int n)
         s->n_effects--;
         free(s->fx[s->n_effects].fir);
         s->fx[s->n_effects].fir = NULL;
+        free(s->fx[s->n_effects].bank);
+        s->fx[s->n_effects].bank = NULL;
         s->dirty = 1;
     }
 }
@@ -214,6 +231,8 @@ int xm_effects_add_biquad(XmEffects *e, const float sos[6])
         }
     }
     e->fx[e->n_effects].kind = 1;
+    e->fx[e->n_effects].fir = NULL;
+    e->fx[e->n_effects].bank = NULL;
     memcpy(e->fx[e->n_effects].sos, sos, sizeof(float) * 6);
     e->n_effects++;
     e->dirty = 1;
@@ -288,6 +307,7 @@ int xm_effects_add_fir(XmEffects *e, const float *h, int K)
     e->fx[e->n_effects].kind = 2;
     e->fx[e->n_effects].n = K;
     e->fx[e->n_effects].fir = c;
+    e->fx[e->n_effects].bank = NULL;
     e->n_effects++;
     e->dirty = 1;
     return XM_OK;
@@ -308,6 +328,7 @@ int xm_effects_add_comb(XmEffects *e, int64_t delay_frames, float b0, float bd, 
     e->fx[e->n_effects].kind = 3;
     e->fx[e->n_effects].n = 0;
     e->fx[e->n_effects].fir = NULL;
+    e->fx[e->n_effects].bank = NULL;
     e->fx[e->n_effects].delay = delay_frames;
     e->fx[e->n_effects].sos[0] = b0;
     e->fx[e->n_effects].sos[1] = bd;
@@ -343,7 +364,88 @@ int xm_effects_add_allpass(XmEffects *e, double delay_ms, double g)
     return xm_effects_add_comb(e, D, -(float)g, 1.0f, -(float)g);
 }
 
+int xm_effects_add_comb_bank(XmEffects *e, const XmCombTap *taps, int n, float dry)
+{
+    if (!e || !taps || n < 1 || n > XM_MAX_BANK || !isfinite(dry)) return XM_EINVAL;
+    for (int k = 0; k < n; ++k) {
+        if (taps[k].delay_frames < 1 || taps[k].delay_frames > XM_MAX_DELAY) return XM_EINVAL;
+        if (!isfinite(taps[k].b0) || !isfinite(taps[k].bd) || !isfinite(taps[k].ad) || !isfinite(taps[k].mix))
+            return XM_EINVAL;
+    }
+    if (e->n_effects >= XM_MAX_EFFECTS) return XM_ENOMEM;
+    XmCombTap *c = malloc(sizeof(XmCombTap) * (size_t)n);   /* the parent's copy first: nothing to undo if it fails */
+    if (!c) return XM_ENOMEM;
+    for (int d = 0; d < e->n_sub; ++d) {   /* multi-device: every device's chain */
+        const int rc = xm_effects_add_comb_bank(e->sub[d], taps, n, dry);
+        if (rc) {
+            drop_last(e, d);   /* every device keeps the same chain */
+            free(c);
+            return rc;
+        }
+    }
+    memcpy(c, taps, sizeof(XmCombTap) * (size_t)n);
+    e->fx[e->n_effects].kind = 4;
+    e->fx[e->n_effects].n = n;
+    e->fx[e->n_effects].fir = NULL;
+    e->fx[e->n_effects].bank = c;
+    e->fx[e->n_effects].sos[0] = dry;
+    e->n_effects++;
+    e->dirty = 1;
+    return XM_OK;
+}
+
+/* undo the last effect of the chain (and of every sub-chain) */
+static void pop_effect(XmEffects *e)
+{
+    drop_last(e, e->n_sub);
+    e->n_effects--;
+    free(e->fx[e->n_effects].fir);
+    e->fx[e->n_effects].fir = NULL;
+    free(e->fx[e->n_effects].bank);
+    e->fx[e->n_effects].bank = NULL;
+    e->dirty = 1;
+}
+
+int xm_effects_add_reverb(XmEffects *e, double rt60_s, double dry, double wet)
+{
+    static const double comb_ms[4] = {29.7, 37.1, 41.1, 43.7}, ap_ms[2] = {5.0, 1.7};
+    if (!e || !isfinite(rt60_s) || !(rt60_s > 0.0) || !isfinite(dry) || !isfinite(wet)) return XM_EINVAL;
+    XmCombTap t[4];
+    for (int k = 0; k < 4; ++k) {
+        const int64_t D = delay_frames_of(e, comb_ms[k]);
+        if (!D) return XM_EINVAL;
+        t[k].delay_frames = D;
+        t[k].b0 = 0.0f;
+        t[k].bd = 1.0f;
+        t[k].ad = -(float)pow(10.0, -3.0 * (double)D / ((double)e->cfg.rate * rt60_s));
+        t[k].mix = (float)wet;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!delay_frames_of(e, ap_ms[k])) return XM_EINVAL;
+    if (!isfinite((float)dry) || !isfinite((float)wet)) return XM_EINVAL;   /* finite in fp64, not in fp32 */
+    if (e->n_effects + 3 > XM_MAX_EFFECTS) return XM_ENOMEM;
+    int rc = xm_effects_add_comb_bank(e, t, 4, (float)dry);
+    if (rc) return rc;
+    for (int k = 0; k < 2; ++k) {
+        rc = xm_effects_add_allpass(e, ap_ms[k], 0.7);
+        if (rc) {   /* all or none */
+            for (int u = 0; u <= k; ++u) pop_effect(e);
+            return rc;
+        }
+    }
+    return XM_OK;
+}
+
 int xm_effects_count(const XmEffects *e) { return e ? e->n_effects : XM_EINVAL; }
+
+int xm_effects_get_comb_bank(const XmEffects *e, int i, XmCombTap taps[XM_MAX_BANK], int *n, float *dry)
+{
+    if (!e || !taps || !n || !dry || i < 0 || i >= e->n_effects || e->fx[i].kind != 4) return XM_EINVAL;
+    memcpy(taps, e->fx[i].bank, sizeof(XmCombTap) * (size_t)e->fx[i].n);
+    *n = e->fx[i].n;
+    *dry = e->fx[i].sos[0];
+    return XM_OK;
+}
 
 int xm_effects_get_comb(const XmEffects *e, int i, int64_t *delay_frames, float coef[3])
 {
@@ -382,6 +484,7 @@ XmEffects *xm_effects_clone_on(const XmEffects *src, int device, int *status)
     for (int i = 0; e && !rc && i < src->n_effects; ++i) {
         if (src->fx[i].kind == 1) rc = xm_effects_add_biquad(e, src->fx[i].sos);
         else if (src->fx[i].kind == 2) rc = xm_effects_add_fir(e, src->fx[i].fir, src->fx[i].n);
+        else if (src->fx[i].kind == 4) rc = xm_effects_add_comb_bank(e, src->fx[i].bank, src->fx[i].n, src->fx[i].sos[0]);
         else rc = xm_effects_add_comb(e, src->fx[i].delay, src->fx[i].sos[0], src->fx[i].sos[1], src->fx[i].sos[2]);
     }
     if (rc) xm_effects_freep(&e);
@@ -418,6 +521,13 @@ static int build_stages(XmEffects *e)
             s->coef_dev = NULL;
             s->delay = e->fx[i].delay;
             memcpy(s->comb, e->fx[i].sos, sizeof(float) * 3);
+            ++i;
+        } else if (e->fx[i].kind == 4) {
+            s->kind = 4;
+            s->n = e->fx[i].n;
+            s->coef_dev = NULL;
+            s->bank_dry = e->fx[i].sos[0];
+            memcpy(s->bank, e->fx[i].bank, sizeof(XmCombTap) * (size_t)s->n);
             ++i;
         } else {
             s->kind = 2;
@@ -463,6 +573,33 @@ static int grow(void **p, size_t *cap, size_t need)
     int rc = xmh_malloc(p, need);
     if (!rc) *cap = need;
     return rc;
+}
+
+int xm_effects_bank_job(const XmEffects *ce, const XmFxStage *s, XmhFxJob *j)
+{
+    XmEffects *e = (XmEffects *)ce;   /* the scratch is a lazily grown cache, like the stages */
+    j->bank_n = s->n;
+    j->bank_dry = s->bank_dry;
+    for (int k = 0; k < s->n; ++k) {
+        j->bank_taps[k].delay = s->bank[k].delay_frames;
+        j->bank_taps[k].b0 = s->bank[k].b0;
+        j->bank_taps[k].bd = s->bank[k].bd;
+        j->bank_taps[k].ad = s->bank[k].ad;
+        j->bank_taps[k].mix = s->bank[k].mix;
+    }
+    if (e->cfg.device == XM_DEVICE_CPU || xmh_bank_ring_floats(j) <= XMH_BANK_LDS_FLOATS) return XM_OK;
+    /* sized by batch: a slot per clip up to the workgroups a launch runs at once */
+    const int slots = j->n_clips < XMH_BANK_SCRATCH_SLOTS ? j->n_clips : XMH_BANK_SCRATCH_SLOTS;
+    const size_t need = (size_t)slots * (size_t)xmh_bank_ring_floats(j) * sizeof(float);
+    if (e->bank_scr_cap < need) {
+        /* an earlier stage's kernel may still run on the old buffer */
+        int rc = xmh_stream_sync(e->stream);
+        if (!rc) rc = grow(&e->bank_scr, &e->bank_scr_cap, need);
+        if (rc) return rc;
+    }
+    j->bank_scratch = e->bank_scr;
+    j->bank_scratch_slots = slots;
+    return XM_OK;
 }
 
 static int ensure_ptrs(XmEffects *e, size_t n)
@@ -513,7 +650,8 @@ static int run_chain(XmEffects *e, size_t batch, size_t frames, float **src, flo
      * If any clip is processed in place and the chain has a FIR stage, first
      * copy the inputs to buf0.  A biquad cascade runs in place (each chunk is
      * read into LDS before its outputs are stored), and so does a comb (the
-     * owner of a sample reads it before it writes it): both take whatever
+     * owner of a sample reads it before it writes it; a bank likewise, with
+     * the inputs it needs again kept in its own delay line): all take whatever
      * (cur, nxt) pair the FIR bookkeeping hands them, equal or not. */
     int inplace = 0, off = 0, has_fir = 0;
     for (int s = 0; s < e->n_stages; ++s) has_fir |= e->stages[s].kind == 2;
@@ -547,6 +685,14 @@ static int run_chain(XmEffects *e, size_t batch, size_t frames, float **src, flo
                 const size_t hoff = clip0 * 2 * (size_t)j.comb_delay * C2;
                 j.comb_hist_in = e->st[s][e->st_cur[s]] + hoff;
                 j.comb_hist_out = e->st[s][e->st_cur[s] ^ 1] + hoff;
+            }
+        } else if (e->stages[s].kind == 4) {
+            rc = xm_effects_bank_job(e, &e->stages[s], &j);
+            if (rc) break;
+            if (streaming) {
+                const size_t hoff = clip0 * (size_t)xmh_bank_hist_floats(&j);
+                j.bank_hist_in = e->st[s][e->st_cur[s]] + hoff;
+                j.bank_hist_out = e->st[s][e->st_cur[s] ^ 1] + hoff;
             }
         } else {
             j.fir = e->stages[s].coef_dev;
@@ -671,9 +817,18 @@ int xm_effects_stream_reset(XmEffects *e, size_t n_clips)
     free_stream_state(e);
     const size_t C = (size_t)e->cfg.channels;
     for (int s = 0; !rc && s < e->n_stages; ++s) {
-        const size_t per = e->stages[s].kind == 1   ? (size_t)e->stages[s].n * 2 * C
-                           : e->stages[s].kind == 3 ? 2 * (size_t)e->stages[s].delay * C
-                                                    : (size_t)(e->stages[s].n - 1) * C;
+        size_t per = e->stages[s].kind == 1   ? (size_t)e->stages[s].n * 2 * C
+                     : e->stages[s].kind == 3 ? 2 * (size_t)e->stages[s].delay * C
+                                              : (size_t)(e->stages[s].n - 1) * C;
+        if (e->stages[s].kind == 4) {   /* every branch's D_k frames, then max D_k frames of input */
+            size_t sum = 0, mx = 0;
+            for (int k = 0; k < e->stages[s].n; ++k) {
+                const size_t D = (size_t)e->stages[s].bank[k].delay_frames;
+                sum += D;
+                mx = D > mx ? D : mx;
+            }
+            per = (sum + mx) * C;
+        }
         if (per == 0) continue;   /* 1-tap FIR: no history */
         const size_t bytes = n_clips * per * sizeof(float);
         const int nbuf = e->stages[s].kind == 1 ? 1 : 2;

@@ -29,14 +29,22 @@ int xm_gain_to_dev(const XmGainRamp *g, XmhGain *d);
 
 /* Effects chain internals (used by the mixer for per-track chains). */
 typedef struct XmFxStage {
-    int kind;              /* 1 = biquad cascade, 2 = FIR, 3 = comb */
-    int n;                 /* sections or taps */
-    float *coef_dev;       /* n*6 (biquad) or n (FIR) floats on device; comb: NULL */
+    int kind;              /* 1 = biquad cascade, 2 = FIR, 3 = comb, 4 = comb bank */
+    int n;                 /* sections, taps or bank branches */
+    float *coef_dev;       /* n*6 (biquad) or n (FIR) floats on device; comb, bank: NULL */
     int64_t delay;         /* comb: D frames */
     float comb[3];         /* comb: b0, bd, ad (travel by value in the job) */
+    float bank_dry;        /* bank: the dry weight and the n branches (by value in the job too) */
+    XmCombTap bank[XM_MAX_BANK];
 } XmFxStage;
 
 int xm_effects_stages(const XmEffects *e, const XmFxStage **stages, int *n_stages);
+/* Fill j's bank fields from stage s of e's chain (kind 4) for a job whose
+ * channels and n_clips are set; on a GPU chain whose delay lines exceed the
+ * LDS budget this grows the device scratch that e owns (XM_ENOMEM) and hands
+ * it to the job.  Work on the stream must be ordered after earlier users of
+ * the scratch (one stream per chain). */
+int xm_effects_bank_job(const XmEffects *e, const XmFxStage *s, XmhFxJob *j);
 #define XM_DEVICE_NONE_ (-2)   /* xm_effects_device of a multi-device chain */
 int xm_effects_device(const XmEffects *e);
 /* the same chain (host coefficient copies replayed) on another device */

@@ -45,6 +45,7 @@ XM_MIXER_IN_CONVERT = 2
 XM_MIXER_PLANAR = 4
 XM_GAIN_RAMP, XM_GAIN_XFADE_OUT = 0, 1
 XM_MAX_DELAY = 1 << 20   # comb stages: frames (include/xm_effects.h)
+XM_MAX_BANK = 8          # branches of a comb bank
 XM_EQ_PEAKING, XM_EQ_LOWSHELF, XM_EQ_HIGHSHELF, XM_EQ_LOWPASS, XM_EQ_HIGHPASS = range(5)
 FMT = {"s16": XM_FMT_S16, "f32": XM_FMT_F32}
 DTYPE = {XM_FMT_S16: np.int16, XM_FMT_F32: np.float32}
@@ -69,6 +70,7 @@ EXPORTED = [
     "xm_audio_mixer_mix_spanning_s16", "xm_effects_create_multi", "xm_effects_n_devices",
     "xm_audio_mixer_last_fast_split", "xm_audio_mixer_set_span_chunks",
     "xm_effects_add_comb", "xm_effects_add_echo", "xm_effects_add_allpass", "xm_effects_get_comb",
+    "xm_effects_add_comb_bank", "xm_effects_get_comb_bank", "xm_effects_add_reverb",
 ]
 
 
@@ -105,6 +107,14 @@ class XmResampleDesign(C.Structure):
 
 
 _vp, _sz, _i, _i64 = C.c_void_p, C.c_size_t, C.c_int, C.c_int64
+
+
+class XmCombTap(C.Structure):
+    """One branch of a comb bank (include/xm_effects.h)."""
+    _fields_ = [("delay_frames", C.c_int64), ("b0", C.c_float), ("bd", C.c_float), ("ad", C.c_float),
+                ("mix", C.c_float)]
+
+
 _sigs = {
     "xm_strerror": (C.c_char_p, [_i]),
     "xm_version": (C.c_char_p, []),
@@ -157,6 +167,9 @@ _sigs = {
     "xm_effects_add_echo": (_i, [_vp, C.c_double, C.c_double, C.c_double]),
     "xm_effects_add_allpass": (_i, [_vp, C.c_double, C.c_double]),
     "xm_effects_get_comb": (_i, [_vp, _i, C.POINTER(_i64), C.POINTER(C.c_float)]),
+    "xm_effects_add_comb_bank": (_i, [_vp, C.POINTER(XmCombTap), _i, C.c_float]),
+    "xm_effects_get_comb_bank": (_i, [_vp, _i, C.POINTER(XmCombTap), C.POINTER(_i), C.POINTER(C.c_float)]),
+    "xm_effects_add_reverb": (_i, [_vp, C.c_double, C.c_double, C.c_double]),
 }
 for _n, (_r, _a) in _sigs.items():
     if os.environ.get("XM_AUDIO_LIB") and not hasattr(_lib, _n):
@@ -488,6 +501,25 @@ class Effects:
 
     def add_allpass(self, delay_ms: float, g: float):
         _check(_lib.xm_effects_add_allpass(self._h, delay_ms, g), "add_allpass")
+
+    def add_comb_bank(self, taps, dry: float):
+        """Parallel combs on the stage's input: taps = [(delay_frames, b0, bd, ad, mix), ...] (1 to
+        XM_MAX_BANK of them), y = dry*x + mix_0*c_0 + mix_1*c_1 + ... in that order."""
+        taps = list(taps)
+        arr = (XmCombTap * max(1, len(taps)))(*[XmCombTap(int(d), b0, bd, ad, mix) for d, b0, bd, ad, mix in taps])
+        _check(_lib.xm_effects_add_comb_bank(self._h, arr, len(taps), dry), "add_comb_bank")
+
+    def add_reverb(self, rt60_s: float, dry: float, wet: float):
+        """Schroeder reverberator: a bank of four feedback combs, then two all-passes (3 effects)."""
+        _check(_lib.xm_effects_add_reverb(self._h, rt60_s, dry, wet), "add_reverb")
+
+    def comb_bank(self, i: int):
+        """([(delay_frames, b0, bd, ad, mix), ...] with float32 coefficients, dry) of comb bank i."""
+        arr, n, dry = (XmCombTap * XM_MAX_BANK)(), _i(0), C.c_float(0)
+        _check(_lib.xm_effects_get_comb_bank(self._h, i, arr, C.byref(n), C.byref(dry)), "get_comb_bank")
+        taps = [(t.delay_frames, np.float32(t.b0), np.float32(t.bd), np.float32(t.ad), np.float32(t.mix))
+                for t in arr[:n.value]]
+        return taps, np.float32(dry.value)
 
     def count(self) -> int:
         return _lib.xm_effects_count(self._h)
